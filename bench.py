@@ -2,7 +2,7 @@
 """
 bench.py — Mpix/s of the panoptic hot path on synthetic 640x480 maps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -21,9 +21,13 @@ all-reduced (RCCL) inside the timed region.  Behind the warm-up the step is capt
 hipGraphs (pipeline per batch stream + metric chain) and replayed; `--no-graph` launches every
 kernel from Python.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  At N=1 the line also
-carries `secondary`: the other BASELINE.json configurations (bf16 logits, configs[2] losses,
-configs[4] shapes + dense cosine loss), measured after the timed region with HIP events.
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up,
+times the K steps and prints the line; `--dump-outputs DIR` also writes what the last timed step
+returned (see `dump_outputs`).  Everything else moves behind `--full`: the `roofline` of the
+dominant kernel (its own isolated pass) and, at N=1, `cpu_baseline` (the C oracle on the host,
+compared with the GPU bit for bit) and `secondary`: the other BASELINE.json configurations (bf16
+logits, configs[2] losses, configs[4] shapes + dense cosine loss), measured after the timed region
+with HIP events.  Without `--full` those fields are null or absent.
 """
 import argparse
 import gc
@@ -73,7 +77,16 @@ def parse_args():
                          'metric chain — so the host queues a step in ~50 us instead of ~170)')
     ap.add_argument('--streams', type=int, default=2,
                     help='batches in flight: consecutive steps alternate over this many HIP streams')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one returned as DIR/<name>.npy '
+                         '(float32 / float64; rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the roofline pass of the dominant '
+                         'kernel and, at N=1, the CPU baseline and the secondary configurations')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def host_cores():
@@ -811,6 +824,64 @@ def secondary(ops, syn, dev):
     return out
 
 
+DUMP_PIXEL_SAMPLE = 1 << 21        # pixels kept of each [B, H, W] map when it holds more
+DUMP_SEED = 20261016
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, r, metrics=None):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy.
+
+    * the [B, H, W] maps of ops.panoptic_pipeline (`semantic_idx_u8`, `instance`, `panoptic`): whole
+      when they hold at most DUMP_PIXEL_SAMPLE pixels, else the same fixed sample of that many flat
+      pixel positions of each (numpy default_rng(DUMP_SEED), sorted); `<map>_image_sums` is the
+      exact per-image sum of the whole map, so that a change outside the sample shows too;
+    * the per-image tables: `n_centers`, `centers_yx`, `center_scores`, `n_ids`, `ids_pan`, `ids_ins`,
+      `pan_of_inst`, `area`; the entries past an image's count of centers / ids are never written
+      (the buffers come from `torch.empty`) and are stored as 0;
+    * with the metric accumulators: `metric_confmat` and `metric_pq`, their totals over every
+      update of the run (warm-up included).
+    float32 where that holds the values exactly, float64 otherwise.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    pan = r['panoptic']
+    dev = pan.device
+    B = pan.shape[0]
+    n_px = pan.numel()
+    pick = None
+    if n_px > DUMP_PIXEL_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, DUMP_PIXEL_SAMPLE, replace=False))
+        pick = torch.from_numpy(pick).to(dev)
+    arrays = {}
+    for name, dt in (('semantic_idx_u8', np.float32), ('instance', np.float32), ('panoptic', np.float64)):
+        t = r[name]
+        arrays[name] = (t if pick is None else t.reshape(-1)[pick]).cpu().numpy().astype(dt)
+        arrays[name + '_image_sums'] = t.reshape(B, -1).sum(1, dtype=torch.int64).cpu().numpy().astype(np.float64)
+
+    def written(t, n):
+        """t [B, K, ...] with the entries k >= n[b] set to 0"""
+        keep = torch.arange(t.shape[1], device=dev).view(1, -1) < n.view(-1, 1).long()
+        return torch.where(keep.view(keep.shape + (1,) * (t.dim() - 2)), t, torch.zeros((), dtype=t.dtype, device=dev))
+    n_c, n_i = r['n_centers'], r['n_ids']
+    arrays['n_centers'] = n_c.cpu().numpy().astype(np.float32)
+    arrays['centers_yx'] = written(r['centers_yx'], n_c).cpu().numpy().astype(np.float32)
+    arrays['center_scores'] = written(r['center_scores'], n_c).cpu().numpy().astype(np.float32)
+    arrays['n_ids'] = n_i.cpu().numpy().astype(np.float32)
+    arrays['ids_pan'] = written(r['ids_pan'], n_i).cpu().numpy().astype(np.float64)
+    arrays['ids_ins'] = written(r['ids_ins'], n_i).cpu().numpy().astype(np.float64)
+    arrays['pan_of_inst'] = r['pan_of_inst'].cpu().numpy().astype(np.float64)
+    arrays['area'] = r['area'].cpu().numpy().astype(np.float64)
+    if metrics is not None:
+        metrics.wait()                      # the copies below queue behind the metric stream
+        arrays['metric_confmat'] = metrics.total_confmat.cpu().numpy().astype(np.float64)
+        arrays['metric_pq'] = metrics.total_pq.cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes, more than the {DUMP_LIMIT_BYTES} allowed')
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return total
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and 'RANK' not in os.environ:
@@ -981,6 +1052,7 @@ def main():
     # of event records costs the pipeline ~4 us, 1.2 % of a K = 20 run when every step carries one
     # (neither the first nor the last step: a replayed step reaches the GPU at once, an eager one
     # over the ~0.17 ms its launches take from Python — at the head and in the tail that is idle time)
+    # (the same schedule with and without --full, which reads these samples: the headline means the same)
     sampled = [i % 8 == 2 and i < args.steps - 1 for i in range(args.steps)]
     if not any(sampled):
         sampled[args.steps // 2] = True
@@ -1047,64 +1119,68 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = n_px_step / (elapsed / args.steps) / 1e6
 
-    # ---- roofline of the dominant kernel (fused argmax + grouping + votes) ----------
-    # algorithmic bytes per launch: logits 4C + offsets 8 read, instance u8 1 written,
-    # per pixel (DESIGN.md "Kernels"); the intermediate sem u8 (1 B/px) is NOT counted
-    fused_ms = float(np.mean([a.elapsed_time(b) for a, b in events]))
-    esize = logits.element_size()
-    fused_bytes_px = esize * C + 8 + 1
-    fused_bytes = fused_bytes_px * B * H * W
-    achieved = fused_bytes / (fused_ms * 1e-3) / 1e9
-    pipeline_bytes_px = esize * C + 4 + 8 + 8 + 1           # 181 B/px at f32, C=40
-    if metrics is not None:
-        pipeline_bytes_px += 8 + 8 + 1                      # + pred pan, target pan, target sem
-    # the same kernel without the metric kernels overlapping on the side stream (untimed)
-    # (200 launches: in a `rocprofv3 --kernel-trace --stats` run of this very command they outnumber
-    # the ~45 launches of warm-up and timed region, so the summary's average duration of the kernel
-    # — profiles/<round>_kernel_stats.csv — is this number to within a few percent)
-    n_iso = 200
-    iso_events = []
-    for _ in range(n_iso + 2):
-        ops.panoptic_pipeline(logits, center, offset, is_thing, want_foreground=False,
-                              fused_kernel_events=iso_events)
-    torch.cuda.synchronize()
-    iso_ms = float(np.mean([a.elapsed_time(b) for a, b in iso_events[2:]]))
-    # HBM bytes per launch from the committed PMC passes of this command (separate
-    # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs, gfx950 wide-stream correction applied by
-    # tools/summarize_profile.py); null when the workload differs from the profiled one
-    traffic = None
-    traffic_sha = None
-    tpath = os.path.join(ROOT, 'profiles', 'latest_traffic.json')
-    if os.path.exists(tpath) and (B, C, H, W) == (32, 40, 480, 640) and esize == 4:
-        import hashlib
-        with open(tpath, 'rb') as f:
-            raw = f.read()
-        traffic_sha = hashlib.sha256(raw).hexdigest()[:16]
-        traffic = next((v.get('hbm_bytes_per_launch') for k, v in json.loads(raw).items()
-                        if k.startswith('k_panoptic_fused')), None)
-    # `frac`: the kernel alone on the chip (the isolated pass above: what a rocprofv3 kernel trace of
-    # this command shows for it); `frac_eager`: HIP events around the launches sampled INSIDE the
-    # timed region — these launches are issued kernel by kernel from Python and queue behind the
-    # other batch in flight, so the figure includes waiting for wave slots and reads lower
-    roofline = {
-        'bound': 'hbm', 'kernel': 'k_panoptic_fused',
-        'achieved': round(fused_bytes / (iso_ms * 1e-3) / 1e9, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-        'frac': round(fused_bytes / (iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-        'kernel_ms': round(iso_ms, 4), 'kernel_launches_isolated': n_iso,
-        'frac_eager': round(achieved / HBM_PEAK_GBS, 4), 'achieved_eager': round(achieved, 1),
-        'kernel_ms_eager': round(fused_ms, 4), 'kernel_launches_timed': len(events),
-        # HBM bytes per launch are NOT measured by this run: a constant from the committed PMC passes
-        # of this command (profiles/latest_traffic.json; its content hash says which)
-        'traffic': traffic, 'traffic_profiled': traffic,
-        'traffic_source': ('profiles/latest_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of '
-                           'this command, per launch, gfx950 wide-stream correction)') if traffic else None,
-        'traffic_profile_sha256': traffic_sha,
-        'algorithmic_bytes_per_launch': fused_bytes,
-        'algorithmic_bytes_per_px': fused_bytes_px,
-        'pipeline_algorithmic_bytes_per_px': pipeline_bytes_px,
-        'pipeline_frac': round(pipeline_bytes_px * B * H * W / (ms_per_step * 1e-3) / 1e9
-                               / HBM_PEAK_GBS, 4),
-    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, metrics)
+    roofline = None
+    if args.full:                              # the roofline takes a pass of its own
+        # ---- roofline of the dominant kernel (fused argmax + grouping + votes) ----------
+        # algorithmic bytes per launch: logits 4C + offsets 8 read, instance u8 1 written,
+        # per pixel (DESIGN.md "Kernels"); the intermediate sem u8 (1 B/px) is NOT counted
+        fused_ms = float(np.mean([a.elapsed_time(b) for a, b in events]))
+        esize = logits.element_size()
+        fused_bytes_px = esize * C + 8 + 1
+        fused_bytes = fused_bytes_px * B * H * W
+        achieved = fused_bytes / (fused_ms * 1e-3) / 1e9
+        pipeline_bytes_px = esize * C + 4 + 8 + 8 + 1           # 181 B/px at f32, C=40
+        if metrics is not None:
+            pipeline_bytes_px += 8 + 8 + 1                      # + pred pan, target pan, target sem
+        # the same kernel without the metric kernels overlapping on the side stream (untimed)
+        # (200 launches: in a `rocprofv3 --kernel-trace --stats` run of this very command they outnumber
+        # the ~45 launches of warm-up and timed region, so the summary's average duration of the kernel
+        # — profiles/<round>_kernel_stats.csv — is this number to within a few percent)
+        n_iso = 200
+        iso_events = []
+        for _ in range(n_iso + 2):
+            ops.panoptic_pipeline(logits, center, offset, is_thing, want_foreground=False,
+                                  fused_kernel_events=iso_events)
+        torch.cuda.synchronize()
+        iso_ms = float(np.mean([a.elapsed_time(b) for a, b in iso_events[2:]]))
+        # HBM bytes per launch from the committed PMC passes of this command (separate
+        # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs, gfx950 wide-stream correction applied by
+        # tools/summarize_profile.py); null when the workload differs from the profiled one
+        traffic = None
+        traffic_sha = None
+        tpath = os.path.join(ROOT, 'profiles', 'latest_traffic.json')
+        if os.path.exists(tpath) and (B, C, H, W) == (32, 40, 480, 640) and esize == 4:
+            import hashlib
+            with open(tpath, 'rb') as f:
+                raw = f.read()
+            traffic_sha = hashlib.sha256(raw).hexdigest()[:16]
+            traffic = next((v.get('hbm_bytes_per_launch') for k, v in json.loads(raw).items()
+                            if k.startswith('k_panoptic_fused')), None)
+        # `frac`: the kernel alone on the chip (the isolated pass above: what a rocprofv3 kernel trace of
+        # this command shows for it); `frac_eager`: HIP events around the launches sampled INSIDE the
+        # timed region — these launches are issued kernel by kernel from Python and queue behind the
+        # other batch in flight, so the figure includes waiting for wave slots and reads lower
+        roofline = {
+            'bound': 'hbm', 'kernel': 'k_panoptic_fused',
+            'achieved': round(fused_bytes / (iso_ms * 1e-3) / 1e9, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': round(fused_bytes / (iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            'kernel_ms': round(iso_ms, 4), 'kernel_launches_isolated': n_iso,
+            'frac_eager': round(achieved / HBM_PEAK_GBS, 4), 'achieved_eager': round(achieved, 1),
+            'kernel_ms_eager': round(fused_ms, 4), 'kernel_launches_timed': len(events),
+            # HBM bytes per launch are NOT measured by this run: a constant from the committed PMC passes
+            # of this command (profiles/latest_traffic.json; its content hash says which)
+            'traffic': traffic, 'traffic_profiled': traffic,
+            'traffic_source': ('profiles/latest_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of '
+                               'this command, per launch, gfx950 wide-stream correction)') if traffic else None,
+            'traffic_profile_sha256': traffic_sha,
+            'algorithmic_bytes_per_launch': fused_bytes,
+            'algorithmic_bytes_per_px': fused_bytes_px,
+            'pipeline_algorithmic_bytes_per_px': pipeline_bytes_px,
+            'pipeline_frac': round(pipeline_bytes_px * B * H * W / (ms_per_step * 1e-3) / 1e9
+                                   / HBM_PEAK_GBS, 4),
+        }
 
     out = {
         'metric': 'Mpix/s panoptic merge+metrics, 640x480xB',
@@ -1133,11 +1209,12 @@ def main():
                        'totals_identical_on_all_ranks': totals_identical,
                        'host_issue_ms_per_step_ranks': host_issue_ranks}
         if dist is not None else None,
+        'full': args.full,
         'roofline': roofline,
     }
 
     solo = rank == 0 and world == 1
-    if solo and not args.no_cpu_baseline:                          # contract: rank 0 at N=1 only
+    if solo and args.full and not args.no_cpu_baseline:            # contract: rank 0 at N=1 only
         cb, (idx, inst, pan) = cpu_baseline(inp, args.cpu_sample_images, C, H, W, metrics)
         n = idx.shape[0]
         ok = bool((r['semantic_idx_u8'][:n].cpu().numpy() == idx).all()
@@ -1147,7 +1224,7 @@ def main():
         out['cpu_baseline'] = cb
     elif rank == 0:
         out['cpu_baseline'] = None
-    if solo and not args.no_secondary:
+    if solo and args.full and not args.no_secondary:
         del inp, logits, center, offset, r, metrics
         torch.cuda.empty_cache()
         out['secondary'] = secondary(ops, syn, dev)

@@ -15,6 +15,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -89,6 +90,53 @@ def test_bench_falls_back_to_gloo_when_rccl_cannot_start():
     assert d['n_gpus'] == 2 and c['backend'] == 'gloo' and c['rccl_ranks'] is None
     assert 'NMSA_BENCH_FORCE_RCCL_FAIL' in c['rccl_error']
     assert c['totals_identical_on_all_ranks'] is True
+
+
+TINY = ['--steps', '3', '--warmup', '2', '--batch-per-gpu', '2', '--height', '96', '--width', '128',
+        '--classes', '8', '--centers', '4']
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """a plain run times the headline only (no roofline pass, CPU baseline or secondary legs);
+    `--dump-outputs` writes the last step's outputs, identical from run to run; the accumulators
+    count exactly the warm-up, graph warm-up and `--steps` updates"""
+    env = dict(os.environ)
+    for k in ('NMSA_BENCH_BACKEND', 'RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    dumps = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + TINY
+                           + ['--dump-outputs', str(tmp_path / run)],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _json_line(r.stdout)
+        assert d['steps'] == 3 and d['warmup'] == 2 and d['ms_per_step'] > 0 and d['value'] > 0
+        assert d['full'] is False and d['roofline'] is None and d['cpu_baseline'] is None
+        assert 'secondary' not in d
+        dumps.append({p.stem: np.load(p) for p in (tmp_path / run).iterdir()})
+    a, b = dumps
+    assert set(a) == set(b) and {'panoptic', 'instance', 'semantic_idx_u8', 'metric_confmat'} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    assert a['panoptic'].shape == (2, 96, 128)
+    graphs = 2 * 2 if d['config']['launch'].startswith('hipGraph') else 0
+    assert a['metric_confmat'].sum() == (2 + graphs + 3) * 2 * 96 * 128
+
+
+def test_bench_full_adds_roofline_and_cpu_baseline():
+    """`--full` measures what the plain run leaves out: the roofline pass and the CPU baseline,
+    whose oracle agrees with the GPU bit for bit (the secondary legs: test below)"""
+    env = dict(os.environ)
+    for k in ('NMSA_BENCH_BACKEND', 'RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--full', '--no-secondary',
+                        '--cpu-sample-images', '2'] + TINY, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d['full'] is True and d['roofline']['kernel_ms'] > 0 and d['roofline']['kernel_launches_isolated'] == 200
+    assert d['cpu_baseline']['gpu_matches_oracle_bit_exact'] is True and d['cpu_baseline']['value'] > 0
 
 
 def test_bench_rejects_a_world_size_mismatch():

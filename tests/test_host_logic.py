@@ -410,6 +410,94 @@ def test_bench_self_launch_command_and_host_cores(monkeypatch, capsys):
     assert cores['cgroup_quota'] is None or cores['usable'] <= max(1, round(cores['cgroup_quota']))
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` on host tensors shaped like a pipeline result: float32 / float64
+    files only, within 64 MB; the table entries the kernels never write are stored as 0; a map larger
+    than the sample is cut at the same seeded positions every time, with exact per-image sums"""
+    import importlib
+    import numpy as np
+    import torch
+    bench = importlib.import_module('bench')
+
+    def result(B, H, W):
+        g = torch.Generator().manual_seed(5)
+        n_c = torch.randint(0, 9, (B,), generator=g, dtype=torch.int32)
+        n_i = torch.minimum(n_c, torch.full_like(n_c, 6))
+        garbage = -7
+        return {
+            'semantic_idx_u8': torch.randint(0, 41, (B, H, W), generator=g).to(torch.uint8),
+            'instance': torch.randint(0, 9, (B, H, W), generator=g).to(torch.uint8),
+            'panoptic': torch.randint(0, 40 << 16, (B, H, W), generator=g),
+            'n_centers': n_c, 'n_ids': n_i,
+            'centers_yx': torch.full((B, 256, 2), garbage, dtype=torch.int32),
+            'center_scores': torch.full((B, 256), float(garbage)),
+            'ids_pan': torch.full((B, 256), garbage, dtype=torch.int64),
+            'ids_ins': torch.full((B, 256), garbage, dtype=torch.int64),
+            'pan_of_inst': torch.randint(0, 40 << 16, (B, 256), generator=g),
+            'area': torch.randint(0, H * W, (B, 256), generator=g, dtype=torch.int32),
+        }
+
+    class Metrics:
+        total_confmat = torch.arange(41 * 41, dtype=torch.int64).view(41, 41)
+        total_pq = torch.linspace(0, 1, 4 * 41, dtype=torch.float64).view(4, 41)
+
+        def wait(self):
+            pass
+
+    small = result(2, 12, 16)
+    assert bench.dump_outputs(str(tmp_path / 'small'), small, Metrics()) <= bench.DUMP_LIMIT_BYTES
+    got = {p.stem: np.load(p) for p in (tmp_path / 'small').iterdir()}
+    assert set(got) == {'semantic_idx_u8', 'instance', 'panoptic', 'semantic_idx_u8_image_sums',
+                        'instance_image_sums', 'panoptic_image_sums', 'n_centers', 'centers_yx',
+                        'center_scores', 'n_ids', 'ids_pan', 'ids_ins', 'pan_of_inst', 'area',
+                        'metric_confmat', 'metric_pq'}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    for k in ('semantic_idx_u8', 'instance', 'panoptic', 'pan_of_inst', 'area'):
+        assert (got[k] == small[k].numpy()).all(), k                     # whole, exact
+    for b in range(2):
+        nc, ni = int(small['n_centers'][b]), int(small['n_ids'][b])
+        assert (got['centers_yx'][b, :nc] == -7).all() and (got['centers_yx'][b, nc:] == 0).all()
+        assert (got['center_scores'][b, nc:] == 0).all() and (got['ids_pan'][b, ni:] == 0).all()
+        assert (got['ids_ins'][b, :ni] == -7).all() and (got['ids_ins'][b, ni:] == 0).all()
+    assert (got['metric_confmat'] == Metrics.total_confmat.numpy()).all()
+    assert (got['metric_pq'] == Metrics.total_pq.numpy()).all()
+
+    big = result(8, 480, 640)                      # 2.46 M pixels: more than the sample
+    n_px = 8 * 480 * 640
+    assert n_px > bench.DUMP_PIXEL_SAMPLE
+    sizes = [bench.dump_outputs(str(tmp_path / d), big) for d in ('a', 'b')]
+    assert sizes[0] == sizes[1] <= bench.DUMP_LIMIT_BYTES
+    pick = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n_px, bench.DUMP_PIXEL_SAMPLE, replace=False))
+    for k in ('semantic_idx_u8', 'instance', 'panoptic'):
+        a, b = np.load(tmp_path / 'a' / f'{k}.npy'), np.load(tmp_path / 'b' / f'{k}.npy')
+        assert a.shape == (bench.DUMP_PIXEL_SAMPLE,) and (a == b).all()
+        assert (a == big[k].reshape(-1).numpy()[pick]).all(), k
+        sums = np.load(tmp_path / 'a' / f'{k}_image_sums.npy')
+        assert sums.dtype == np.float64
+        assert (sums == big[k].reshape(8, -1).sum(1, dtype=torch.int64).numpy()).all(), k
+    assert not (tmp_path / 'a' / 'metric_confmat.npy').exists()
+
+
+def test_bench_full_and_dump_options():
+    """a plain run measures the headline only; `--full` adds the rest; `--steps` must be positive"""
+    import importlib
+    import sys
+    bench = importlib.import_module('bench')
+    old = sys.argv
+    try:
+        sys.argv = ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2']
+        a = bench.parse_args()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+        sys.argv = ['bench.py', '--full', '--dump-outputs', 'out']
+        a = bench.parse_args()
+        assert a.full and a.dump_outputs == 'out'
+        sys.argv = ['bench.py', '--steps', '0']
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+    finally:
+        sys.argv = old
+
+
 def test_metric_copies_keep_their_own_compute():
     """the rank-sync wrapper of `compute()` lives on the class: deepcopy / pickle of a metric give
     independent metrics (a wrapper bound to the instance would keep computing the original)"""

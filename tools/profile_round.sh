@@ -6,7 +6,7 @@
 # /opt/skills/guides/MI355X_MICROARCH.md prescribes — kernel trace + stats; --pmc FETCH_SIZE;
 # --pmc WRITE_SIZE (counters never combined with tracing domains other than --kernel-trace; the
 # program itself follows `--`) — then the summaries under profiles/<tag>_* and
-# profiles/<tag>_<leg>_*, and one plain bench.py run whose JSON line is kept next to them.
+# profiles/<tag>_<leg>_*, and one `bench.py --full` run whose JSON line is kept next to them.
 set -e -o pipefail
 TAG=${1:-r02x}
 LEGS=${2:-"cfg2_bf16 cfg3_losses cfg5_bf16 ce150 cos512 cos768 next_rows api cfg5_full"}
@@ -36,9 +36,9 @@ summarize() {           # <name> <tag suffix> [bench log]
 
 if [ -z "$LEGS_ONLY" ]; then
 mkdir -p "$OUT/headline"
-three_passes headline "$ROOT/bench.py" --steps 30 --warmup 10 --no-cpu-baseline --no-secondary
-echo "[profile] plain bench"
-(cd "$ROOT" && timeout -k 10 400 python3 bench.py > "$OUT/bench.log" 2> "$OUT/bench.err")
+three_passes headline "$ROOT/bench.py" --steps 30 --warmup 10 --full --no-cpu-baseline --no-secondary
+echo "[profile] full bench"
+(cd "$ROOT" && timeout -k 10 400 python3 bench.py --full > "$OUT/bench.log" 2> "$OUT/bench.err")
 summarize headline "" "$OUT/bench.log"
 fi
 for leg in $LEGS; do
