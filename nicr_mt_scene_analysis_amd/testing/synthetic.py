@@ -305,6 +305,74 @@ def make_label_maps(batch_size, n_classes=41, height=480, width=640, n_instances
     return {'semantic': sem, 'instance': ins, 'semantic_classes_is_thing': is_thing}
 
 
+WORD_EDGES = (64, 128, 192)           # class words of the thing LUT as ballot masks (C > 64)
+
+
+def wide_edge_classes(n_classes: int) -> np.ndarray:
+    """the classes next to the 64-class word edges (63/64, 127/128, 191/192), the last one and 0"""
+    near = {c for e in WORD_EDGES + (256,) for c in (e - 2, e - 1, e, e + 1)}
+    return np.array(sorted(c for c in near | {0, n_classes - 1} if 0 <= c < n_classes))
+
+
+def make_wide_class_inputs(batch_size: int, n_classes: int, height: int, width: int,
+                           n_centers, seed: int, levels: int = 4, p_edge: float = 0.5,
+                           p_tie: float = 0.3, p_thing: float = 0.5, p_far: float = 0.2
+                           ) -> Dict[str, np.ndarray]:
+    """Panoptic inputs for 49..256 classes, aimed at the class-word edges.
+
+    Logits are small integer levels (int8; exact in bf16 / f16, and equal logits give equal
+    probabilities, so the first index wins under any softmax).  The winning class of a pixel is
+    drawn with a bias toward the word edges; with probability `p_tie` it is tied with the class
+    on the other side of an edge (63/64, 127/128, 191/192).  The two classes of an edge pair are
+    one thing and one stuff class.  The heat map holds `n_centers` (an int or one per image)
+    isolated peaks of distinct heights on a 2-pixel lattice inside the border: a 3x3 NMS keeps
+    every one and the top-k has no tie.  Every offset points exactly at the pixel's nearest
+    peak, or with probability `p_far` at a random one."""
+    rng = np.random.default_rng(seed)
+    B, C, H, W = batch_size, n_classes, height, width
+    logits = rng.integers(0, levels, (B, C, H, W)).astype(np.int8)
+    edge = wide_edge_classes(C)
+    top = np.where(rng.random((B, H, W)) < p_edge, rng.choice(edge, (B, H, W)),
+                   rng.integers(0, C, (B, H, W)))
+    edges = [e for e in WORD_EDGES if e < C]
+    tie = (rng.random((B, H, W)) < p_tie) if edges else np.zeros((B, H, W), bool)
+    if edges:
+        top = np.where(tie, rng.choice(edges, (B, H, W)) - 1, top)
+    np.put_along_axis(logits, top[:, None], np.int8(levels + 1), axis=1)
+    partner = np.where(tie, top + 1, top)
+    np.put_along_axis(logits, partner[:, None], np.int8(levels + 1), axis=1)
+
+    is_thing = rng.random(C) < p_thing
+    for e in edges:
+        is_thing[e - 1] = rng.random() < 0.5
+        is_thing[e] = not is_thing[e - 1]
+    if C == 256:
+        is_thing[255] = True
+
+    heat = np.zeros((B, 1, H, W), np.float32)
+    offset = np.zeros((B, 2, H, W), np.float32)
+    # (the reference's NMS pads the pooled map with zeros: a peak on the border is never kept)
+    sites = np.stack(np.meshgrid(np.arange(1, H - 1, 2), np.arange(1, W - 1, 2), indexing='ij'), -1)
+    sites = sites.reshape(-1, 2)
+    yy = np.arange(H)[:, None]
+    xx = np.arange(W)[None, :]
+    per_image = np.broadcast_to(np.asarray(n_centers), (B,))
+    for b in range(B):
+        n = int(min(per_image[b], len(sites)))
+        if n == 0:
+            continue
+        cyx = sites[rng.choice(len(sites), n, replace=False)]
+        heights = 0.15 + 0.85 * (rng.permutation(n) + 1) / n
+        heat[b, 0, cyx[:, 0], cyx[:, 1]] = heights.astype(np.float32)
+        d2 = (cyx[:, 0, None, None] - yy) ** 2 + (cyx[:, 1, None, None] - xx) ** 2
+        k = d2.argmin(0)
+        k = np.where(rng.random((H, W)) < p_far, rng.integers(0, n, (H, W)), k)
+        offset[b, 0] = ((cyx[k, 0] - yy) / H).astype(np.float32)
+        offset[b, 1] = ((cyx[k, 1] - xx) / W).astype(np.float32)
+    return {'semantic_logits': logits, 'instance_center': heat, 'instance_offset': offset,
+            'semantic_classes_is_thing': is_thing}
+
+
 def input_digest(*arrays: np.ndarray) -> str:
     h = hashlib.sha256()
     for a in arrays:

@@ -176,6 +176,27 @@ def gen_panoptic(ref):
              digest=jdump(digest), **panoptic_outputs(r, score_stride=8))
 
 
+def gen_wide_classes(ref):
+    """150 and 256 classes: thing classes on both sides of the 64-class word edges, argmax ties
+    across them, more than 64 centers (C = 256: ids past the first k_assign pass)"""
+    print('panoptic pipeline, 150 / 256 classes (reference PanopticPostprocessing.postprocess)')
+    kw = dict(top_k_instances=250)
+    out = {}
+    for C, n_centers, seed in ((150, [100, 70], 41), (256, [230, 150], 42)):
+        inp = syn.make_wide_class_inputs(2, C, 32, 48, n_centers, seed=seed)
+        lg = inp['semantic_logits']
+        run_inp = dict(inp, semantic_logits=lg.astype(np.float32))
+        r = run_panoptic(ref, run_inp, heatmap_kwargs=kw)
+        res = panoptic_outputs(r)
+        # class value 256 (index 255 + 1) does not fit the uint8 of the other fixtures
+        res['panoptic_semantic'] = r['panoptic_segmentation_deeplab_semantic_idx'].numpy()
+        assert res['meta_n'].min() > 64, res['meta_n']
+        assert C < 256 or res['ids_ins'].max() >= 36864 // (C + 1)    # a row of the second pass
+        out.update({f'c{C}__in_{k}': v for k, v in inp.items()})
+        out.update({f'c{C}__{k}': v for k, v in res.items()})
+    save('panoptic_wide_classes', kwargs=jdump(kw), classes=np.array([150, 256], np.int32), **out)
+
+
 def gen_edges(ref):
     """degenerate images: no centers, no foreground, all foreground with one center, a tight
     distance threshold that un-assigns most pixels."""
@@ -1220,6 +1241,8 @@ def main():
         gen_panoptic(ref)
     if want('edges'):
         gen_edges(ref)
+    if want('wide_classes'):
+        gen_wide_classes(ref)
     if want('centers'):
         gen_centers(ref)
     if want('grouping'):

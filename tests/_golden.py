@@ -31,6 +31,18 @@ def ids_from_arrays(n, k, v):
             for b in range(len(n))]
 
 
+def wide_class_cases():
+    """(C, case) of tests/golden/panoptic_wide_classes.npz (150 and 256 classes): each case
+    holds the keys of the other panoptic fixtures, the int8 logits rebuilt as float32"""
+    g = load('panoptic_wide_classes')
+    for C in g['classes'].tolist():
+        pfx = f'c{C}__'
+        case = {k[len(pfx):]: g[k] for k in g.files if k.startswith(pfx)}
+        case['in_semantic_logits'] = case['in_semantic_logits'].astype(np.float32)
+        case['kwargs'] = g['kwargs']
+        yield C, case
+
+
 def cos_emb_large_cases():
     """(name, params, inputs, golden) of tests/golden/cos_emb_large.npz: the inputs are
     regenerated from the seed and checked against the stored digest"""

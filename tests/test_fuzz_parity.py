@@ -104,6 +104,12 @@ def test_fuzz_argmax_probability_ties(oracle, seed, C, scale, spread, dtype):
     `spread` below (every column its own softmax denominator; 120: beyond Sleef's cut-off) — the
     kernels (stand-alone, with score, fused) against the C oracle, two independent restatements
     of the same arithmetic, and a sample against the numpy twin"""
+    _EFFECTIVE['argmax_ties'] = _EFFECTIVE.get('argmax_ties', 0) + \
+        check_argmax_probability_ties(oracle, seed, C, scale, spread, dtype)
+
+
+def check_argmax_probability_ties(oracle, seed, C, scale, spread, dtype):
+    """-> the number of pixels where the probability rule beats the plain argmax"""
     from _golden import aten_softmax_argmax
     from nicr_mt_scene_analysis_amd import ops
     rng = np.random.default_rng(seed)
@@ -145,7 +151,7 @@ def test_fuzz_argmax_probability_ties(oracle, seed, C, scale, spread, dtype):
         assert (g.cpu().numpy() == want).all()
     twin, _ = aten_softmax_argmax(x[:, :, :4])
     assert (twin == want[:, :4]).all()
-    _EFFECTIVE['argmax_ties'] = _EFFECTIVE.get('argmax_ties', 0) + int((want != x.argmax(axis=1)).sum())
+    return int((want != x.argmax(axis=1)).sum())
 
 
 @settings(max_examples=_n(40), deadline=None, derandomize=_DERANDOMIZE,
@@ -158,9 +164,11 @@ def test_fuzz_pipeline_medium_shapes_vs_oracle(oracle, p):
     check_pipeline(oracle, p, max_centers=4096)
 
 
-def check_pipeline(oracle, p, max_centers=1024):
+def check_pipeline(oracle, p, max_centers=1024, inputs=None):
+    """`inputs`: (logits, heat, offset, is_thing) made by the caller instead of make_inputs(p);
+    -> the oracle's results, or None where the check ends early"""
     from nicr_mt_scene_analysis_amd import ops
-    logits, heat, offset, is_thing = make_inputs(p)
+    logits, heat, offset, is_thing = make_inputs(p) if inputs is None else inputs
     B, C, H, W = logits.shape
     idx, score = oracle.semantic_argmax(logits)
     fg = is_thing[idx]
@@ -194,6 +202,7 @@ def check_pipeline(oracle, p, max_centers=1024):
     assert (r['panoptic'] == pan).all(), p
     got = ids_from_arrays(r['n_ids'], r['ids_pan'], r['ids_ins'])
     assert [list(d.items()) for d in got] == [list(d.items()) for d in ids], p
+    return dict(idx=idx, fg=fg, n=n, inst=inst, pan=pan, ids=ids)
 
 
 @settings(max_examples=_n(120), deadline=None, derandomize=_DERANDOMIZE,

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from _golden import load, jload, ids_from_arrays
+from _golden import load, jload, ids_from_arrays, meta_from_arrays, wide_class_cases
 from nicr_mt_scene_analysis_amd.testing import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +84,61 @@ def test_pipeline_cfg1_vs_golden(ops, name):
     r = run_hip_pipeline(ops, inp['semantic_logits'], inp['instance_center'],
                          inp['instance_offset'], inp['semantic_classes_is_thing'])
     check_against_golden(g, r)
+
+
+@pytest.mark.parametrize('dtype', ['float32', 'bfloat16', 'float16'])
+def test_pipeline_wide_classes_vs_golden(ops, dtype):
+    """150 / 256 classes (the thing LUT in four ballot words, > 64 centers, C = 256: ids in the
+    second pass of the vote table through LDS) against the reference's outputs; the integer
+    logit levels are exact in every logits dtype"""
+    for C, g in wide_class_cases():
+        kw = jload(g['kwargs'])
+        x = dev(g['in_semantic_logits']).to(getattr(torch, dtype))
+        r = ops.panoptic_pipeline(
+            x, dev(g['in_instance_center']), dev(g['in_instance_offset']),
+            dev(g['in_semantic_classes_is_thing']), top_k=kw['top_k_instances'],
+            want_score=True, want_panoptic_semantic=True)
+        torch.cuda.synchronize()
+        check_against_golden(g, {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v)
+                                 for k, v in r.items()})
+
+
+def test_postprocess_api_wide_classes_vs_golden():
+    """the reference-shaped PanopticPostprocessing.postprocess at 150 / 256 classes"""
+    from nicr_mt_scene_analysis_amd.data.preprocessing import APPLIED_PREPROCESSING_KEY
+    from nicr_mt_scene_analysis_amd.model.postprocessing import get_postprocessing_class
+    for C, g in wide_class_cases():
+        is_thing = tuple(bool(t) for t in g['in_semantic_classes_is_thing'])
+        post = get_postprocessing_class('panoptic')(
+            semantic_postprocessing=get_postprocessing_class('semantic')(),
+            instance_postprocessing=get_postprocessing_class('instance')(**jload(g['kwargs'])),
+            semantic_classes_is_thing=is_thing, semantic_class_has_orientation=is_thing)
+        B, _, H, W = g['in_semantic_logits'].shape
+        batch = {'rgb_fullres': torch.zeros((B, 3, H, W)),
+                 APPLIED_PREPROCESSING_KEY: [[{'type': 'Resize', 'valid_region_slice_y': slice(0, H),
+                                               'valid_region_slice_x': slice(0, W)}]] * B}
+        data = ((dev(g['in_semantic_logits']),
+                 (dev(g['in_instance_center']), dev(g['in_instance_offset']))), (None, None))
+        r = post.postprocess(data, batch, is_training=False)
+        assert (r['semantic_segmentation_idx'].cpu().numpy() == g['semantic_idx']).all(), C
+        np.testing.assert_allclose(r['semantic_segmentation_score'].cpu().numpy(),
+                                   g['semantic_score'], rtol=1e-5, atol=1e-7)
+        assert (r['panoptic_foreground_mask'].cpu().numpy() == g['foreground']).all(), C
+        assert (r['panoptic_segmentation_deeplab_instance_idx'].cpu().numpy() == g['instance']).all()
+        assert (r['panoptic_segmentation_deeplab'].cpu().numpy() == g['panoptic']).all(), C
+        assert (r['panoptic_segmentation_deeplab_semantic_idx'].cpu().numpy()
+                == g['panoptic_semantic']).all(), C
+        want = ids_from_arrays(g['ids_n'], g['ids_pan'], g['ids_ins'])
+        for a, b in zip(r['panoptic_segmentation_deeplab_ids'], want):
+            assert list(a.items()) == list(b.items()), C
+        want_meta = meta_from_arrays(g['meta_n'], g['meta_center_yx'], g['meta_area'],
+                                     g['meta_score'])
+        for a, b in zip(r['panoptic_segmentation_deeplab_instance_meta'], want_meta):
+            assert a.keys() == b.keys(), C
+            for i in a:
+                assert a[i]['center_yx'] == b[i]['center_yx']
+                assert a[i]['area'] == b[i]['area']
+                assert a[i]['score'] == b[i]['score']
 
 
 @pytest.mark.parametrize('shape', [(3, 7, 50, 37), (2, 40, 120, 160), (1, 150, 96, 128)])

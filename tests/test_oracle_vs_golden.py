@@ -6,7 +6,7 @@ reference's known-answer PQ tables (reference tests/test_metrics.py:76-446).
 import numpy as np
 import pytest
 
-from _golden import load, jload, meta_from_arrays, ids_from_arrays
+from _golden import load, jload, meta_from_arrays, ids_from_arrays, wide_class_cases
 from nicr_mt_scene_analysis_amd.testing import synthetic as syn
 
 
@@ -74,6 +74,33 @@ def test_pipeline_cfg1(oracle, name):
     r = _run_pipeline_oracle(oracle, inp['semantic_logits'], inp['instance_center'],
                              inp['instance_offset'], inp['semantic_classes_is_thing'])
     _check_pipeline(g, r)
+
+
+def test_pipeline_wide_classes(oracle):
+    """150 and 256 classes: argmax ties across the 64-class word edges, thing classes on both
+    sides of them, more than 64 centers and (C = 256) instance ids past the first pass of the
+    vote table through LDS"""
+    seen = set()
+    for C, g in wide_class_cases():
+        kw = jload(g['kwargs'])
+        r = _run_pipeline_oracle(oracle, g['in_semantic_logits'], g['in_instance_center'],
+                                 g['in_instance_offset'], g['in_semantic_classes_is_thing'], kw)
+        _check_pipeline(g, r)
+        assert (r['pan'] // (1 << 16) == g['panoptic_semantic']).all()
+        idx, fg = g['semantic_idx'].astype(np.int64), g['foreground']
+        assert (g['meta_n'] > 64).all()
+        # the fixture reaches what it is for: things on every class word, wins by the lower index
+        # of a tie across an edge
+        for lo in (64, 128, 192):
+            if lo < C:
+                assert (fg & (idx >= lo) & (idx < lo + 64)).sum() > 0, (C, lo)
+                x = g['in_semantic_logits']
+                tied = (x[:, lo - 1] == x.max(axis=1)) & (x[:, lo] == x[:, lo - 1])
+                assert (idx[tied] == lo - 1).all() and tied.sum() > 0, (C, lo)
+        seen.add(C)
+        if C == 256:
+            assert g['ids_ins'].max() >= 36864 // (C + 1)
+    assert seen == {150, 256}
 
 
 # ---------------------------------------------------------------------------
