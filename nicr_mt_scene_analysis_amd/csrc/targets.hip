@@ -1614,6 +1614,30 @@ int tg_scan_px_per_wg(int B, int P, size_t lds, int resident_per_cu)
     return (int)px;
 }
 
+// zero `bytes` bytes at `p` (8-byte aligned) with a kernel.  Not hipMemsetAsync: captured into a
+// hipGraph, the memset of a workspace was not performed again on the second and later replays on
+// the MI355X (tests/test_state_sequences.py), and the next call read the tables the previous
+// replay left behind.  A kernel node replays like every other launch of the call.
+__global__ void k_tg_zero(unsigned char* __restrict__ p, size_t bytes)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n8 = bytes >> 3;
+    for (size_t k = i; k < n8; k += stride) ((uint2*)p)[k] = make_uint2(0u, 0u);
+    for (size_t k = (n8 << 3) + i; k < bytes; k += stride) p[k] = 0;
+}
+
+int tg_zero(void* p, size_t bytes, hipStream_t stream)
+{
+    if (bytes == 0) return NMSA_OK;
+    if ((uintptr_t)p % 8) return NMSA_ERR_ARG;
+    size_t blocks = ((bytes >> 3) + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(k_tg_zero, dim3((unsigned)blocks), dim3(256), 0, stream, (unsigned char*)p, bytes);
+    return check_launch();
+}
+
 int tg_common(const void* sem, int sem_dtype, const void* ins, int ins_dtype, int B, int NC, int P,
               int W, int cap, bool moments, unsigned char* ws, size_t need, int32_t* status,
               hipStream_t stream, const uint8_t* is_thing_class = nullptr, int32_t* encoded_ids = nullptr,
@@ -1629,7 +1653,7 @@ int tg_common(const void* sem, int sem_dtype, const void* ins, int ins_dtype, in
         // scan dirtied): no memset then.  The status word is SET by the call's last tail.
         const size_t hbytes = (size_t)B * tg_hash_bytes(cap, NC) + TG_GLOBAL_BYTES;
         int rc = NMSA_OK;
-        if (!workspace_is_clean && (rc = check_hip(hipMemsetAsync(hs, 0, hbytes, stream)))) return rc;
+        if (!workspace_is_clean && (rc = tg_zero(hs, hbytes, stream))) return rc;
         const size_t lds = tg_scan_lds_bytes(cap, moments);
         const bool small = tg_hash_slots(cap) <= 1024;
         // ONE round of resident workgroups: what the registers and the LDS of this instantiation admit
@@ -1658,7 +1682,7 @@ int tg_common(const void* sem, int sem_dtype, const void* ins, int ins_dtype, in
         if (did_tail) *did_tail = true;
         return check_launch();
     }
-    int rc = check_hip(hipMemsetAsync(ws, 0, (size_t)B * tg_image_bytes(cap, NC), stream));
+    int rc = tg_zero(ws, (size_t)B * tg_image_bytes(cap, NC), stream);
     if (rc) return rc;
     const int gx = tg_grid_x(P);
     const bool fast = tg_fast(sem, sem_dtype, ins, ins_dtype, P);

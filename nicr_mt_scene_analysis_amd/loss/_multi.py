@@ -18,6 +18,7 @@ policy state.
 """
 import ctypes as C
 import weakref
+from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -42,33 +43,48 @@ _STATES: 'weakref.WeakSet[SpecState]' = weakref.WeakSet()
 class SpecState:
     """device-resident spec records of the totals of one caller: int32 [n_totals + 1, 8]
     ([0] confirmed, [1] recomputed, [2] w as fp32 bits, [5] flags; see csrc/losses_multi.hip);
-    the last row is scratch of the calls (the tickets of their launches), zero between calls"""
+    the last row is scratch of the calls (the tickets of their launches), zero between calls.
+
+    One record set per (device, stream): the tickets of a launch are only right while no launch on
+    another stream draws from the same row, and the learned factors are per stream as well (a
+    validation loop on a side stream learns its own).  At most `MAX_RECORDS` sets are kept (least
+    recently used first out); a dropped set is forgotten like after `reset()`: its stream starts
+    again from the initial factors."""
+
+    MAX_RECORDS = 8
 
     def __init__(self, n_totals: int, initial_weight=1.0) -> None:
         assert 1 <= n_totals <= MAX_TOTALS
         self.n_totals = n_totals
-        self._w0 = [float(initial_weight)] * n_totals if not isinstance(initial_weight, (list, tuple)) \
-            else [float(v) for v in initial_weight]
-        self._rec: Dict[torch.device, torch.Tensor] = {}
+        self._w0 = [float(v) for v in initial_weight] if isinstance(initial_weight, (list, tuple)) \
+            else [float(initial_weight)] * n_totals
+        self._rec: 'OrderedDict[Tuple[torch.device, int], torch.Tensor]' = OrderedDict()
         _STATES.add(self)
 
     def records(self, dev) -> torch.Tensor:
+        """the record set of `dev` on its current stream (made on first use)"""
         dev = torch.device(dev)
         if dev.type == 'cuda' and dev.index is None:
             dev = torch.device('cuda', torch.cuda.current_device())
-        r = self._rec.get(dev)
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else 0)
+        r = self._rec.get(key)
         if r is None:
-            host = torch.zeros((self.n_totals + 1, 8), dtype=torch.int32)
-            host.view(torch.float32)[:self.n_totals, 2] = torch.tensor(self._w0, dtype=torch.float32)
-            r = self._rec[dev] = host.to(dev)
+            # made on the device (no host copy: a set first used inside a graph capture is allowed)
+            r = torch.zeros((self.n_totals + 1, 8), dtype=torch.int32, device=dev)
+            for t, w in enumerate(self._w0):
+                r.view(torch.float32)[t, 2].fill_(w)
+            self._rec[key] = r
+            while len(self._rec) > self.MAX_RECORDS:
+                self._rec.popitem(last=False)
+        else:
+            self._rec.move_to_end(key)
         return r
 
     def reset(self) -> None:
-        for dev in list(self._rec):
-            del self._rec[dev]
+        self._rec.clear()
 
     def stats(self) -> Dict[str, int]:
-        """host sync"""
+        """summed over the record sets of every device and stream (host sync)"""
         out = {'confirmed': 0, 'recomputed': 0}
         for r in self._rec.values():
             v = r[:self.n_totals, :2].sum(dim=0).tolist()
@@ -77,7 +93,7 @@ class SpecState:
         return out
 
     def weights(self, dev) -> List[float]:
-        """the learned upstream factors (host sync; tests, diagnostics)"""
+        """the upstream factors learned on `dev`'s current stream (host sync; tests, diagnostics)"""
         return self.records(dev).view(torch.float32)[:self.n_totals, 2].tolist()
 
 # where a forward-written gradient lives (tools/diag_cos_relalign.py swaps it to place the buffer)

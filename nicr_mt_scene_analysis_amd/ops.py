@@ -383,7 +383,9 @@ def _gauss_lut(sigma: int, dev: torch.device) -> torch.Tensor:
 
 # Persistent workspaces of the target generators, one per (device, stream, B, classes,
 # max_instances): on the on-wire layout a call leaves its hash tables zeroed, so the next call on
-# the same workspace skips the memset (`workspace_is_clean`).  LRU of 4.
+# the same workspace skips the memset (`workspace_is_clean`).  LRU of 4.  A hipGraph captured on a
+# stream that has no workspace yet makes one inside the capture and zeroes it on every replay (a
+# kernel in csrc/targets.hip, tg_zero: a captured hipMemsetAsync was not redone on later replays).
 _TARGET_WORKSPACES: 'collections.OrderedDict[tuple, list]' = __import__('collections').OrderedDict()
 
 

@@ -166,6 +166,7 @@ def test_fuzz_pipeline_medium_shapes_vs_oracle(oracle, p):
 
 def check_pipeline(oracle, p, max_centers=1024, inputs=None):
     """`inputs`: (logits, heat, offset, is_thing) made by the caller instead of make_inputs(p);
+    p['normalized'] = False (default True): the offsets are taken as pixels, unscaled;
     -> the oracle's results, or None where the check ends early"""
     from nicr_mt_scene_analysis_amd import ops
     logits, heat, offset, is_thing = make_inputs(p) if inputs is None else inputs
@@ -184,7 +185,7 @@ def check_pipeline(oracle, p, max_centers=1024, inputs=None):
         threshold=p['thr'],
         kernel_size=p['ksize'], top_k=p['topk'], apply_foreground_mask=p['apply_fg'],
         distance_threshold=p['dist_thr'], want_score=True, want_panoptic_semantic=True,
-        max_centers=max_centers)
+        max_centers=max_centers, normalized_offset=p.get('normalized', True))
     torch.cuda.synchronize()
     r = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in r.items()}
     assert (r['semantic_idx_u8'] == idx).all(), p
@@ -196,7 +197,9 @@ def check_pipeline(oracle, p, max_centers=1024, inputs=None):
         assert (r['center_scores'][b, :n[b]] == scores[b, :n[b]]).all(), p
     if n.max() > 255:
         return                      # uint8 wrap of the ids is pinned by the golden fixture only
-    inst, area = oracle.group_offsets(offset, fg, cyx, n, scale_y=H, scale_x=W, dist_thr=p['dist_thr'])
+    scale = (H, W) if p.get('normalized', True) else (1.0, 1.0)
+    inst, area = oracle.group_offsets(offset, fg, cyx, n, scale_y=scale[0], scale_x=scale[1],
+                                      dist_thr=p['dist_thr'])
     assert (r['instance'] == inst).all(), p
     pan, ids = oracle.deeplab_merge(idx + 1, inst, fg, 1 << 16, np.where(is_thing)[0] + 1, 0)
     assert (r['panoptic'] == pan).all(), p
