@@ -742,6 +742,30 @@ int nmsa_multitask_loss_bwd_unless(const nmsa_loss_item* items_host, int n_items
                                    int32_t* counters, void* workspace, size_t workspace_bytes,
                                    nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * DenseVisualEmbeddingPostprocessing._postprocess_inference, normalisation + projection
+ *     model/postprocessing/dense_visual_embedding.py:126 (output /= output.norm(dim=1)) and :81
+ *     (F.conv2d with the C x D x 1 x 1 class embeddings), both heads from one pass over `emb`.
+ *   emb        f32 [B,D,H,W]  normalised IN PLACE: x * (1 / sqrt(sum_d x^2)) per pixel
+ *   weight_a/b f32 [Ca,D] / [Cb,D] or NULL (head off; its C and logits are then ignored)
+ *   logits_a/b f32 [B,Ca,H,W] / [B,Cb,H,W]: dot(x, w_c) * (1 / sqrt(sum_d x^2))
+ * A zero vector gives NaN in its D channels and in every logit; inf / NaN propagate.  f32 products
+ * and accumulation throughout.  D % 4 == 0 (<= 1024), H*W % 4 == 0, C <= 256 per head and 16-byte
+ * aligned pointers take the MFMA kernel; every other shape (any D, C >= 1) a plain per-pixel
+ * kernel, which NMSA_DVE_ROUTE_GENERIC also selects for shapes the MFMA kernel accepts (tests).
+ * Without the 1 / sqrt the reference's x / sqrt(sum) stays finite a little longer: a pixel whose sum
+ * of squares leaves the normal float32 range (every |x| below ~1e-19, or one above ~1.8e19) gets
+ * inf or 0 as its factor here.  Supported magnitudes are those whose sum of squares is a normal
+ * float32.  NMSA_ERR_ARG: NULL / non-positive arguments, H*W above 2^31 - 1, more than 2^31 - 1
+ * workgroups.  No workspace.
+ * ------------------------------------------------------------------------- */
+#define NMSA_DVE_ROUTE_AUTO 0
+#define NMSA_DVE_ROUTE_GENERIC 1
+int nmsa_dve_project(float* emb, int B, int D, int H, int W,
+                     const float* weight_a, int Ca, float* logits_a,
+                     const float* weight_b, int Cb, float* logits_b,
+                     int route, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

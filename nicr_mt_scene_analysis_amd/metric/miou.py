@@ -87,7 +87,10 @@ class MeanIntersectionOverUnion(Metric):
             sum_pred = sum_pred - cm[0, 1:].float()
         has_gt = sum_gt != 0                               # classes without GT do not count
         iou = tp[has_gt] / (sum_pred[has_gt] + sum_gt[has_gt] - tp[has_gt])
-        miou = iou.mean()
+        # the mean alone on the host, where the reference takes it (miou.py:92): the per-class
+        # IoUs are exact integer sums and one IEEE division each, but a float32 mean reduced on
+        # the device adds in another order and differs from the reference's in the last bit
+        miou = iou.cpu().mean().to(iou.device)
         if not return_ious:
             return miou
         ious = torch.full((self._n_classes,), float('nan'), dtype=torch.float32,

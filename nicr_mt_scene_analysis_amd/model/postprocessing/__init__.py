@@ -1,18 +1,20 @@
 """Postprocessing factory (reference model/postprocessing/__init__.py:24-44).
 
-On the hot path: 'semantic', 'instance', 'panoptic'.  'normal', 'scene' and
-'dense-visual-embedding' are other tasks' postprocessors (resize / softmax / a
-conv2d GEMM) and out of scope of this package."""
+On the hot path: 'semantic', 'instance', 'panoptic' and 'dense-visual-embedding' (in-place
+normalisation + projection onto the class embeddings on HIP, class maps through the semantic
+path).  'normal' and 'scene' are other tasks' postprocessors (resize / softmax) and out of scope
+of this package."""
 from typing import Any
 
 from ...utils import partial_class
 from .base import PostprocessingBase
 from .dense_base import DensePostprocessingBase
+from .dense_visual_embedding import DenseVisualEmbeddingPostprocessing
 from .instance import InstancePostprocessing
 from .panoptic import PanopticPostprocessing
 from .semantic import SemanticPostprocessing
 
-_OUT_OF_SCOPE = ('normal', 'scene', 'dense-visual-embedding')
+_OUT_OF_SCOPE = ('normal', 'scene')
 
 
 def get_postprocessing_class(name: str, **kwargs: Any):
@@ -22,6 +24,8 @@ def get_postprocessing_class(name: str, **kwargs: Any):
         cls = InstancePostprocessing
     elif name == 'panoptic':
         cls = PanopticPostprocessing
+    elif name == 'dense-visual-embedding':
+        cls = DenseVisualEmbeddingPostprocessing
     elif name in _OUT_OF_SCOPE:
         raise NotImplementedError(
             f"postprocessing '{name}' is not part of the MI355X hot path; use the "

@@ -28,32 +28,42 @@ class SemanticPostprocessing(DensePostprocessingBase):
         return {'semantic_output': output, 'semantic_side_outputs': side_outputs}
 
     @staticmethod
-    def _argmax_entries(r: LazyDict, logits: torch.Tensor, suffix: str = '') -> None:
+    def _keys(prefix: str = '', stem: str = 'semantic_segmentation'):
+        """(logits, softmax, score, idx) keys: the semantic task's own by default; another task
+        that derives class maps from logits (dense visual embedding) passes its prefix and stem"""
+        return (prefix + 'semantic_output', prefix + 'semantic_softmax_scores',
+                prefix + stem + '_score', prefix + stem + '_idx')
+
+    @staticmethod
+    def _argmax_entries(r: LazyDict, logits: torch.Tensor, suffix: str = '', prefix: str = '',
+                        stem: str = 'semantic_segmentation') -> None:
         """idx now; the softmax tensor and the score of the winning class when they are read
         (semantic.py:52-59 / :71-80): the argmax alone needs no exponentials, and validation
         loops only consume the class map."""
+        _, k_sm, k_score, k_idx = (k + suffix for k in SemanticPostprocessing._keys(prefix, stem))
         narrow = logits.shape[1] <= 256
         am = ops.semantic_argmax(logits, want_u8=narrow, want_i64=not narrow, want_score=False)
-        r.set_lazy('semantic_softmax_scores' + suffix, lambda: ops.semantic_softmax(logits))
-        r.set_lazy('semantic_segmentation_score' + suffix,
+        r.set_lazy(k_sm, lambda: ops.semantic_softmax(logits))
+        r.set_lazy(k_score,
                    lambda: ops.semantic_argmax(logits, want_u8=False, want_i64=False,
                                                want_score=True)['score'])
         if narrow:      # uint8 class map for the metrics, the reference's int64 map when read
             idx_u8 = am['idx_u8']
-            r.aux['semantic_segmentation_idx' + suffix] = idx_u8
-            r.set_lazy('semantic_segmentation_idx' + suffix, lambda: idx_u8.long())
+            r.aux[k_idx] = idx_u8
+            r.set_lazy(k_idx, lambda: idx_u8.long())
         else:
-            r['semantic_segmentation_idx' + suffix] = am['idx']
+            r[k_idx] = am['idx']
 
-    def _fullres_entries(self, r: LazyDict, output: torch.Tensor, batch: BatchType) -> None:
+    @staticmethod
+    def _fullres_entries(r: LazyDict, output: torch.Tensor, batch: BatchType, prefix: str = '',
+                         stem: str = 'semantic_segmentation') -> None:
         """semantic.py:61-80.  With a real resize, idx / score come from ONE fused pass over the
         network-resolution logits (`nmsa_semantic_argmax_resized`); the full-resolution logits
         and their softmax are produced only when somebody reads them."""
         crop, shape = get_valid_region_slices_and_fullres_shape(batch, 'semantic')
         cropped = output[..., crop[0], crop[1]]
-        k_out, k_sm, k_score, k_idx = (get_fullres_key(k) for k in (
-            'semantic_output', 'semantic_softmax_scores', 'semantic_segmentation_score',
-            'semantic_segmentation_idx'))
+        keys = SemanticPostprocessing._keys(prefix, stem)
+        k_out, k_sm, k_score, k_idx = (get_fullres_key(k) for k in keys)
         if tuple(cropped.shape[-2:]) != tuple(shape):
             r.set_lazy(k_out, lambda: ops.resize_bilinear(output, shape, crop))
             r.set_derived(k_sm, lambda d: ops.semantic_softmax(d[k_out]))
@@ -73,8 +83,7 @@ class SemanticPostprocessing(DensePostprocessingBase):
         if cropped.shape == output.shape:
             # nothing was cropped or resized: the fullres entries are the same
             # functions of the same logits -> share them (bit-identical)
-            for k in ('semantic_softmax_scores', 'semantic_segmentation_score',
-                      'semantic_segmentation_idx'):
+            for k in keys[1:]:
                 if r.is_pending(k):
                     r.set_derived(get_fullres_key(k), (lambda kk: (lambda d: d[kk]))(k))
                 else:
@@ -82,7 +91,9 @@ class SemanticPostprocessing(DensePostprocessingBase):
                 if k in r.aux:
                     r.aux[get_fullres_key(k)] = r.aux[k]
         else:
-            self._argmax_entries(r, cropped.contiguous(), suffix='_fullres')
+            # (the full-resolution keys are the plain keys + '_fullres')
+            SemanticPostprocessing._argmax_entries(r, cropped.contiguous(), suffix='_fullres',
+                                                   prefix=prefix, stem=stem)
 
     def _postprocess_inference(
         self, data: DecoderRawOutputType, batch: BatchType

@@ -547,6 +547,55 @@ def dve_targets(
     return {'indices': idx, 'lut': lut}
 
 
+def dve_project(
+    emb: torch.Tensor,
+    weight_a: Optional[torch.Tensor] = None,
+    weight_b: Optional[torch.Tensor] = None,
+    *,
+    generic: bool = False,
+) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """reference: DenseVisualEmbeddingPostprocessing (dense_visual_embedding.py:126 + :81) —
+    `emb /= emb.norm(dim=1, keepdim=True)` IN PLACE, then `F.conv2d(emb, weight[:, :, None, None])`
+    for up to two [C, D] class-embedding matrices, all from one pass over `emb`.  Returns
+    (logits_a, logits_b); None for a head that is off.  `generic` selects the plain per-pixel
+    kernel on shapes the MFMA kernel would take (tests)."""
+    if emb.dtype != torch.float32:
+        raise TypeError(f'emb must be float32, got {emb.dtype}')
+    if not emb.is_cuda:
+        raise L.NmsaError(f'emb is on {emb.device}: the HIP path needs tensors on the MI355X '
+                          '(there is no CPU fallback).')
+    if emb.ndim != 4:
+        raise ValueError(f'emb must be [B, D, H, W], got shape {tuple(emb.shape)}')
+    B, D, H, W = (int(n) for n in emb.shape)
+    dev = emb.device
+    heads = []
+    for name, w in (('weight_a', weight_a), ('weight_b', weight_b)):
+        if w is None:
+            heads.append((None, 0, None))
+            continue
+        if w.dtype != torch.float32:
+            raise TypeError(f'{name} must be float32, got {w.dtype}')
+        w = L.require_device_tensor(w, name)
+        if w.device != dev:
+            raise ValueError(f'{name} is on {w.device}, emb on {dev}')
+        if w.ndim == 4 and w.shape[2:] == (1, 1):       # the reference's conv2d weight
+            w = w[:, :, 0, 0].contiguous()
+        if w.ndim != 2 or int(w.shape[1]) != D or int(w.shape[0]) < 1:
+            raise ValueError(f'{name} must be [C, {D}], got shape {tuple(w.shape)}')
+        Cn = int(w.shape[0])
+        heads.append((w, Cn, torch.empty((B, Cn, H, W), dtype=torch.float32, device=dev)))
+    # cold path: a strided map is normalised through a contiguous copy and copied back
+    x = emb if emb.is_contiguous() else emb.contiguous()
+    if x.numel():
+        (wa, Ca, la), (wb, Cb, lb) = heads
+        L.check(L.lib().nmsa_dve_project(
+            L.ptr(x), B, D, H, W, L.ptr(wa), Ca, L.ptr(la), L.ptr(wb), Cb, L.ptr(lb),
+            1 if generic else 0, L.stream_ptr(dev)), 'nmsa_dve_project')
+        if x is not emb:
+            emb.copy_(x)
+    return heads[0][2], heads[1][2]
+
+
 # ----------------------------------------------------------------------------- a5
 def panoptic_merge(
     semantic: torch.Tensor,

@@ -129,12 +129,14 @@ class DenseVisualEmbeddingTaskHelper(TaskHelperBase):
     def validation_step(self, batch, batch_idx, predictions_post):
         loss_dict = self._compute_losses(batch, batch_idx, predictions_post)
         target = get_fullres(batch, 'semantic')
+        aux = getattr(predictions_post, 'aux', {})
         for key, metric in (('dense_visual_embedding_text_based_semantic_idx', self._text_metric_iou),
                             ('dense_visual_embedding_visual_mean_based_semantic_idx',
                              self._visual_mean_metric_iou)):
             k = get_fullres_key(key)
             if k in predictions_post:
-                metric.update_masked_void(predictions_post[k], target)
+                # uint8 twin of the int64 class map when the postprocessor offers one
+                metric.update_masked_void(aux[k] if k in aux else predictions_post[k], target)
         return loss_dict, {}
 
     @append_profile_to_logs('semantic_epoch_end_time')

@@ -426,3 +426,52 @@ def make_panoptic_inputs_torch(batch_size, n_classes=40, height=480, width=640,
     is_thing = torch.arange(Cn, device=device) >= Cn // 2
     return {'semantic_logits': logits.contiguous(), 'instance_center': center,
             'instance_offset': offset, 'semantic_classes_is_thing': is_thing}
+
+
+# ---- dense-visual-embedding postprocessing cases (tests/golden/dve_postprocess.npz) ----------
+# name -> (B, D, H, W, Ca, Cb or 0, crop (y0, y1, x0, x1), full-resolution shape)
+DVE_POST_RECIPES = {
+    'clean': (2, 512, 120, 160, 40, 40, (4, 116, 0, 160), (150, 200)),
+    'noise': (2, 512, 120, 160, 40, 0, (0, 120, 0, 160), (120, 160)),
+    'wide': (2, 768, 96, 128, 150, 0, (0, 96, 0, 128), (96, 200)),
+    'odd': (1, 66, 45, 61, 37, 300, (2, 43, 3, 60), (41, 57)),
+}
+
+
+def make_dve_post_inputs(recipe: str, seed: int) -> Dict[str, np.ndarray]:
+    """Embedding map, class embeddings and a full-resolution semantic target of one recipe.  Only
+    generator draws and elementwise float32 arithmetic (no reductions), so the bytes are the same
+    on every host.  'clean': 8x8 blocks of one class each, pixel = (class row + 0.08 noise) * a
+    per-pixel scale in 0.5-4.5; the others: pure N(0, 1); 'odd' has one all-zero pixel and one inf."""
+    B, D, H, W, Ca, Cb, crop, full = DVE_POST_RECIPES[recipe]
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    w_a = rng.standard_normal((Ca, D), dtype=f32) * f32(1.0 / np.sqrt(D))
+    w_b = None
+    if Cb:
+        if recipe == 'clean':       # "visual mean" rows: the text rows, perturbed
+            w_b = w_a + rng.standard_normal((Cb, D), dtype=f32) * f32(0.3 / np.sqrt(D))
+        else:
+            w_b = rng.standard_normal((Cb, D), dtype=f32) * f32(1.0 / np.sqrt(D))
+    n_classes = Ca
+    if recipe == 'clean':
+        cls = rng.integers(0, Ca, (B, (H + 7) // 8, (W + 7) // 8))
+        cls = np.repeat(np.repeat(cls, 8, axis=1), 8, axis=2)[:, :H, :W]
+        noise = rng.standard_normal((B, D, H, W), dtype=f32)
+        scale = f32(0.5) + f32(4.0) * rng.random((B, 1, H, W), dtype=f32)
+        emb = (np.moveaxis(w_a[cls], -1, 1) + f32(0.08) * noise) * scale
+        # target: the block's class (+1; 0 = void on a sparse grid) seen from the full resolution
+        yy = crop[0] + (np.arange(full[0]) * (crop[1] - crop[0])) // full[0]
+        xx = crop[2] + (np.arange(full[1]) * (crop[3] - crop[2])) // full[1]
+        target = (cls[:, yy][:, :, xx] + 1).astype(np.uint8)
+        target[:, ::7, ::5] = 0
+    else:
+        emb = rng.standard_normal((B, D, H, W), dtype=f32)
+        target = rng.integers(0, n_classes + 1, (B,) + tuple(full)).astype(np.uint8)
+    if recipe == 'odd':
+        emb[0, :, 7, 11] = 0.0
+        emb[0, 5, 20, 33] = np.inf
+    out = {'emb': np.ascontiguousarray(emb, dtype=f32), 'weight_a': w_a, 'semantic_fullres': target}
+    if w_b is not None:
+        out['weight_b'] = np.ascontiguousarray(w_b, dtype=f32)
+    return out
