@@ -766,6 +766,42 @@ int nmsa_dve_project(float* emb, int B, int D, int H, int W,
                      const float* weight_b, int Cb, float* logits_b,
                      int route, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * the surface-normal task (csrc/normal.hip)
+ *
+ * nmsa_normal_valid_mask: _get_valid_gt_normals, task_helper/normal.py:165-167
+ *   target f32 [B,3,H,W] -> mask u8 [B,H,W]: 0 iff all three channels compare equal to zero BY
+ *   VALUE (-0.0 is zero; a NaN channel makes the pixel valid, as `==` does), else 1.  One pass;
+ *   16-byte loads when H*W % 4 == 0 and the pointers are aligned, per-pixel loads otherwise.
+ *
+ * nmsa_rmse_update: RootMeanSquaredError.update, metric/rmse.py:30-57
+ *   *sum_state += sum over the selected pixels of sqrt(mean_c (pred - target)^2), *count_state +=
+ *   their number.  Both are DEVICE pointers (the metric's f64 / i64 states); atomic adds, one per
+ *   workgroup and state: no host sync, capturable in a hipGraph, a replay adds again.
+ *   pred     f32|bf16|f16, widened to f32 before the subtraction (torch's type promotion)
+ *   target   f32 [B,C,H,W], 1 <= C <= 8
+ *   mask_mode NMSA_RMSE_MASK_NONE (mask NULL: every pixel), _GIVEN (mask u8 [B,H,W], non-0 = use),
+ *            _FROM_TARGET (mask NULL, C == 3: the rule of nmsa_normal_valid_mask on `target`)
+ *   source   Hs == 0 and Ws == 0: pred is [B,C,H,W].  Otherwise pred is [B,C,Hs,Ws] at the network
+ *            resolution and target pixel (y, x) reads pred[.., y0 + sy(y), x0 + sx(x)] with the
+ *            nearest-neighbour arithmetic of nmsa_resize_nearest over the valid region (y0, x0, h,
+ *            w): `update(resize_nearest(pred[crop]), target)` without the full-resolution map.
+ *   Per pixel: float32 subtract, square, sequential channel sum, divide by C, square root, every
+ *   step IEEE-rounded; the sums are float64.  A pixel the mask leaves out contributes nothing
+ *   whatever it holds (the reference gathers).  NMSA_ERR_ARG: NULL / non-positive arguments, C
+ *   outside 1..8, a mask pointer that does not fit the mode, a valid region outside the source,
+ *   planes above 2^30 pixels.  No workspace.
+ * ------------------------------------------------------------------------- */
+#define NMSA_RMSE_MASK_NONE 0
+#define NMSA_RMSE_MASK_GIVEN 1
+#define NMSA_RMSE_MASK_FROM_TARGET 2
+int nmsa_normal_valid_mask(const float* target, int B, int H, int W, uint8_t* mask,
+                           nmsa_stream_t stream);
+int nmsa_rmse_update(const void* pred, int pred_dtype, const float* target, const uint8_t* mask,
+                     int mask_mode, int B, int C, int H, int W,
+                     int Hs, int Ws, int y0, int x0, int h, int w,
+                     double* sum_state, int64_t* count_state, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

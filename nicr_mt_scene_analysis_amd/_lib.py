@@ -84,6 +84,9 @@ _SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     'nmsa_dve_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'nmsa_dve_project': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    'nmsa_normal_valid_mask': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'nmsa_rmse_update': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                              _vp, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -29,22 +29,13 @@
 #include <algorithm>
 #include <cmath>
 #include "nmsa_common.hpp"
+#include "crop_resize.hpp"
 #include "argmax_state.hpp"
 
 namespace nmsa {
 namespace {
 
-struct CropResize {
-    int Hs, Ws;        // source plane size
-    int y0, x0, h, w;  // valid region inside the source plane
-    int Ho, Wo;        // output plane size
-    float sy, sx;      // float(h)/float(Ho), float(w)/float(Wo)
-};
-
-__device__ __forceinline__ int nearest_src(float scale, int dst, int in)
-{
-    return min((int)floorf(__fmul_rn((float)dst, scale)), in - 1);
-}
+// CropResize, nearest_src, bad_geometry, make_geometry: crop_resize.hpp (shared with normal.hip)
 
 __device__ __forceinline__ void bilinear_src(float scale, int dst, int in,
                                              int& i0, int& i1, float& w0, float& w1)
@@ -752,23 +743,6 @@ int launch_tile(const void* src, const CropResize& g, TilePlan plan, int planes,
     if (plan.k16 == 1)
         return launch_tile_k<DTYPE, MODE, 1>(src, g, plan.pra_lg, planes, group, idx_u8, idx_i64, score, dst, stream);
     return launch_tile_k<DTYPE, MODE, 2>(src, g, plan.pra_lg, planes, group, idx_u8, idx_i64, score, dst, stream);
-}
-
-bool bad_geometry(int planes, int Hs, int Ws, int y0, int x0, int h, int w, int Ho, int Wo)
-{
-    if (planes <= 0 || Hs <= 0 || Ws <= 0 || h <= 0 || w <= 0 || Ho <= 0 || Wo <= 0) return true;
-    if (y0 < 0 || x0 < 0 || (int64_t)y0 + h > Hs || (int64_t)x0 + w > Ws) return true;
-    if ((int64_t)Hs * Ws > ((int64_t)1 << 30) || (int64_t)Ho * Wo > ((int64_t)1 << 30)) return true;
-    return false;
-}
-
-CropResize make_geometry(int Hs, int Ws, int y0, int x0, int h, int w, int Ho, int Wo)
-{
-    CropResize g;
-    g.Hs = Hs; g.Ws = Ws; g.y0 = y0; g.x0 = x0; g.h = h; g.w = w; g.Ho = Ho; g.Wo = Wo;
-    g.sy = (float)h / (float)Ho;      // ATen compute_scales_value<float>
-    g.sx = (float)w / (float)Wo;
-    return g;
 }
 
 template <typename T, bool VIA_F32>

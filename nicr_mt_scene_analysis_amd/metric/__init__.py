@@ -1,7 +1,7 @@
-"""Metric accumulators of the hot path (reference metric/__init__.py).
-`RootMeanSquaredError` belongs to the normals task and is out of scope."""
+"""Metric accumulators of the hot path (reference metric/__init__.py)."""
 from .base import Metric
 from .mae import MeanAbsoluteAngularError
 from .mae import PanopticQualityWithOrientationMAE
 from .miou import MeanIntersectionOverUnion
 from .pq import PanopticQuality
+from .rmse import RootMeanSquaredError

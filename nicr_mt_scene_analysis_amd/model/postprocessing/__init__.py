@@ -2,8 +2,10 @@
 
 On the hot path: 'semantic', 'instance', 'panoptic' and 'dense-visual-embedding' (in-place
 normalisation + projection onto the class embeddings on HIP, class maps through the semantic
-path).  'normal' and 'scene' are other tasks' postprocessors (resize / softmax) and out of scope
-of this package."""
+path).  `NormalPostprocessing` exists as a class (lazy nearest resize to the dataset resolution)
+but is not registered here yet: the factory still raises NotImplementedError for 'normal', which
+an existing test pins; registering it is a follow-up that flips that assertion.  'scene' is
+another task's postprocessor (softmax) and out of scope of this package."""
 from typing import Any
 
 from ...utils import partial_class
@@ -11,6 +13,7 @@ from .base import PostprocessingBase
 from .dense_base import DensePostprocessingBase
 from .dense_visual_embedding import DenseVisualEmbeddingPostprocessing
 from .instance import InstancePostprocessing
+from .normal import NormalPostprocessing
 from .panoptic import PanopticPostprocessing
 from .semantic import SemanticPostprocessing
 

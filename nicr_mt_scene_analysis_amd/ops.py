@@ -596,6 +596,86 @@ def dve_project(
     return heads[0][2], heads[1][2]
 
 
+# ----------------------------------------------------------------------------- normals
+RMSE_MASK_NONE, RMSE_MASK_GIVEN, RMSE_MASK_FROM_TARGET = 0, 1, 2
+
+
+def _require_on_device(t: torch.Tensor, name: str) -> None:
+    if not t.is_cuda:
+        raise L.NmsaError(f'{name} is on {t.device}: the HIP path needs tensors on the MI355X '
+                          '(there is no CPU fallback).')
+
+
+def normal_valid_mask(target: torch.Tensor) -> torch.Tensor:
+    """reference: `_get_valid_gt_normals` (task_helper/normal.py:165-167) — bool [B,H,W], False
+    where all three channels of `target` [B,3,H,W] equal zero (by value: -0.0 counts, NaN does
+    not), from one pass over the target."""
+    if target.dtype != torch.float32:
+        raise TypeError(f'target must be float32, got {target.dtype}')
+    _require_on_device(target, 'target')
+    if target.ndim != 4 or target.shape[1] != 3:
+        raise ValueError(f'target must be [B, 3, H, W], got shape {tuple(target.shape)}')
+    t = target.contiguous()
+    B, _, H, W = (int(n) for n in t.shape)
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=t.device)
+    if mask.numel():
+        L.check(L.lib().nmsa_normal_valid_mask(L.ptr(t), B, H, W, L.ptr(mask), L.stream_ptr(t.device)),
+                'nmsa_normal_valid_mask')
+    return mask.view(torch.bool)
+
+
+def rmse_update(sum_state: torch.Tensor, count_state: torch.Tensor, preds: torch.Tensor,
+                target: torch.Tensor, mask=None, crop=None) -> None:
+    """reference: `RootMeanSquaredError.update` (metric/rmse.py:30-57) into the metric's device
+    states: sum_state (float64 scalar) += sum_px sqrt(mean_c (preds - target)^2), count_state
+    (int64 scalar) += pixels, no host sync.  `mask`: None, a bool / uint8 [B,H,W] tensor, or
+    'target' (valid-normal rule of `normal_valid_mask`, evaluated on the fly).  `preds` has the
+    target's shape, or — with `crop` = the valid-region slices, or any other spatial size — is
+    the network-resolution map that `resize_nearest(preds, target.shape[-2:], crop)` would bring
+    to the target's resolution; that map is then never written."""
+    if target.dtype != torch.float32:
+        raise TypeError(f'target must be float32, got {target.dtype}')
+    code = L.float_dtype_code(preds)                # TypeError for anything but f32 / bf16 / f16
+    for name, t in (('preds', preds), ('target', target), ('sum_state', sum_state),
+                    ('count_state', count_state)):
+        _require_on_device(t, name)
+    if sum_state.dtype != torch.float64 or count_state.dtype != torch.int64 or \
+            sum_state.numel() != 1 or count_state.numel() != 1:
+        raise TypeError('the states are one float64 and one int64 element')
+    if preds.ndim != 4 or target.ndim != 4 or preds.shape[:2] != target.shape[:2]:
+        raise ValueError(f'preds / target must be [B, C, H, W] with the same B and C, got '
+                         f'{tuple(preds.shape)} / {tuple(target.shape)}')
+    p, t = preds.contiguous(), target.contiguous()
+    B, C, H, W = (int(n) for n in t.shape)
+    if not 1 <= C <= 8:
+        raise ValueError(f'1 to 8 channels are supported, got {C}')
+    source = (0, 0, 0, 0, 0, 0)
+    if crop is not None or tuple(p.shape[-2:]) != (H, W):
+        source = _crop_geometry(p, crop)
+        if source == (H, W, 0, 0, H, W):
+            # the crop is the whole map and nothing is resized: the prediction IS at the target's
+            # resolution, read it with whole-group loads instead of per-pixel gathers
+            source = (0, 0, 0, 0, 0, 0)
+    if isinstance(mask, str):
+        if mask != 'target':
+            raise ValueError(f"mask must be None, a tensor or 'target', got '{mask}'")
+        if C != 3:
+            raise ValueError("mask='target' is the rule for 3-channel normals")
+        mode, m = RMSE_MASK_FROM_TARGET, None
+    elif mask is None:
+        mode, m = RMSE_MASK_NONE, None
+    else:
+        _require_on_device(mask, 'mask')
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError(f'mask must be [B, H, W] = {(B, H, W)}, got {tuple(mask.shape)}')
+        mode, m = RMSE_MASK_GIVEN, _u8(mask)
+    if t.numel() == 0:
+        return
+    L.check(L.lib().nmsa_rmse_update(
+        L.ptr(p), code, L.ptr(t), L.ptr(m), mode, B, C, H, W, *source,
+        L.ptr(sum_state), L.ptr(count_state), L.stream_ptr(t.device)), 'nmsa_rmse_update')
+
+
 # ----------------------------------------------------------------------------- a5
 def panoptic_merge(
     semantic: torch.Tensor,

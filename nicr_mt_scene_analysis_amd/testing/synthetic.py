@@ -475,3 +475,57 @@ def make_dve_post_inputs(recipe: str, seed: int) -> Dict[str, np.ndarray]:
     if w_b is not None:
         out['weight_b'] = np.ascontiguousarray(w_b, dtype=f32)
     return out
+
+
+# ---- surface-normal task cases (tests/golden/normal_task.npz) ---------------------------------
+# name -> (B, network resolution (H, W), crop (y0, y1, x0, x1), full resolution, supervision scales)
+NORMAL_RECIPES = {
+    'same': (2, (8, 12), (0, 8, 0, 12), (8, 12), (1, 2, 4)),
+    'up': (2, (6, 8), (1, 6, 0, 7), (9, 13), (1, 2)),
+    'holes': (3, (8, 8), (0, 8, 0, 8), (16, 16), (1,)),
+    'wide': (1, (4, 260), (0, 4, 2, 258), (4, 512), (1,)),
+}
+
+
+def _normal_target(rng, B: int, H: int, W: int, holes: bool) -> np.ndarray:
+    """unit normals [B,3,H,W] with exact zeros in 4x4-block blobs of about 30 % of the image; the
+    last image keeps its first block valid.  `holes`: image 0 entirely invalid, some invalid
+    pixels carry -0.0, some valid ones have one or two zero channels."""
+    f32 = np.float32
+    v = rng.standard_normal((B, 3, H, W), dtype=f32)
+    norm = np.sqrt(v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1] + v[:, 2] * v[:, 2])
+    t = (v / np.maximum(norm, f32(1e-6))[:, None]).astype(f32)
+    blob = rng.random((B, (H + 3) // 4, (W + 3) // 4)) < 0.3
+    blob[-1, 0, 0] = False
+    invalid = np.repeat(np.repeat(blob, 4, axis=1), 4, axis=2)[:, :H, :W].copy()
+    if holes:
+        invalid[0] = True
+    t = np.where(invalid[:, None], f32(0.0), t).astype(f32)
+    if holes:
+        b = B - 1
+        t[0, 1, ::2, ::3] = f32(-0.0)               # invalid pixels, some channels -0.0
+        t[0, :, 1, 1] = f32(-0.0)
+        t[b, :, 0, 0] = (0.0, 0.0, 1.0)             # two zero channels: valid
+        t[b, :, 0, 1] = (0.0, 0.6, 0.8)             # one zero channel: valid
+        t[b, :, 0, 2] = (-0.0, 0.0, -1.0)
+    return np.ascontiguousarray(t)
+
+
+def make_normal_inputs(recipe: str, seed: int) -> Dict[str, np.ndarray]:
+    """Predictions and targets of every supervision scale ('pred_s<k>', 'target_s<k>'), the
+    full-resolution target and an explicit metric mask of one recipe.  Generator draws and
+    elementwise float32 arithmetic only, so the bytes are the same on every host.  Predictions are
+    finite everywhere: target + 0.3 N(0, 1)."""
+    B, (Hn, Wn), crop, (H, W), scales = NORMAL_RECIPES[recipe]
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    holes = recipe == 'holes'
+    out = {}
+    for s in scales:
+        h, w = Hn // s, Wn // s
+        t = _normal_target(rng, B, h, w, holes)
+        out[f'target_s{s}'] = t
+        out[f'pred_s{s}'] = (t + f32(0.3) * rng.standard_normal((B, 3, h, w), dtype=f32)).astype(f32)
+    out['target_fullres'] = _normal_target(rng, B, H, W, holes)
+    out['metric_mask'] = rng.random((B, H, W)) < 0.6
+    return out
