@@ -317,6 +317,20 @@ int nmsa_instance_orientation_wide(const float* orientation, const void* instanc
  *     keys i64 [B,K] (first n_keys[b] valid), embeddings f32 [B,K,D], image_embedding f32 [B,D];
  *     lut f32 [B,K,D] = normalise(embedding - diff_factor * image_embedding) (NULL: indices only);
  *     indices i32 [B,H,W] = 1 + position of the pixel's panoptic id in keys (0 = none)
+ *  nmsa_orientation_targets    OrientationTargetGenerator._preprocess data/preprocessing/orientation.py:37-97
+ *     estimate_class u8 [n_classes] or NULL (no class test); keys i32 [B,K] (K <= 4096): per image
+ *     the instance ids that have an orientation, strictly ascending, the first n_keys[b] valid;
+ *     n_keys i32 [B]; biternion f32 [B,K,2] = (cos, sin) per key, 8-byte aligned.
+ *     An id > 0 is painted over its whole mask iff it occurs in the map, is one of the image's keys
+ *     and (estimate_class given) its majority class over the whole mask (void counts, a tie goes
+ *     to the smaller class) is flagged.  orientation f32 [B,2,H,W] (channel 0 cos, 1 sin: the
+ *     collated CHW form of the reference's HWC image), foreground u8 [B,H,W], present u8 [B,K]
+ *     (1 for exactly the painted keys); everything else +0.0 / 0: every byte of the three outputs
+ *     is written.  status bits 1, 32, 64; workspace and workspace_is_clean as for
+ *     nmsa_instance_targets (the three calls may share one workspace in any order).
+ *     launches: the scan of nmsa_instance_targets (or memset + 4 on any other layout) + one paint
+ *     launch (k_ot_paint: ids looked up in the scan's id table; NMSA_OT_LOOKUP=search, read per call:
+ *     binary search over the keys in LDS); no host synchronisation, no allocation.
  * ------------------------------------------------------------------------- */
 size_t nmsa_targets_workspace_bytes(int B, int n_classes, int max_instances);
 int nmsa_instance_clear_stuff(const void* semantic, int sem_dtype, void* instance, int ins_dtype,
@@ -338,6 +352,13 @@ int nmsa_panoptic_targets(const void* semantic, int sem_dtype, const void* insta
                           int64_t* panoptic, int64_t* ids_pan, int64_t* ids_ins, int32_t* n_ids,
                           int32_t* status, void* workspace, size_t workspace_bytes, int workspace_is_clean,
                           nmsa_stream_t stream);
+int nmsa_orientation_targets(const void* semantic, int sem_dtype, const void* instance, int ins_dtype,
+                             const uint8_t* estimate_class, const int32_t* keys, const int32_t* n_keys,
+                             const float* biternion, int B, int n_classes, int H, int W, int K,
+                             int max_instances,
+                             float* orientation, uint8_t* foreground, uint8_t* present,
+                             int32_t* status, void* workspace, size_t workspace_bytes, int workspace_is_clean,
+                             nmsa_stream_t stream);
 int nmsa_dve_targets(const int64_t* panoptic, const int64_t* keys, const int32_t* n_keys,
                      const float* embeddings, const float* image_embedding, float diff_factor,
                      int B, int K, int D, int H, int W,

@@ -82,6 +82,8 @@ _SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     'nmsa_panoptic_targets': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    'nmsa_orientation_targets': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
+                                      _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     'nmsa_dve_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'nmsa_dve_project': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
     'nmsa_normal_valid_mask': (_i, [_vp, _i, _i, _i, _vp, _vp]),

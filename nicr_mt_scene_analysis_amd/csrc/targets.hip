@@ -1561,6 +1561,124 @@ __global__ __launch_bounds__(256) void k_ow_export(unsigned char* __restrict__ w
     if (threadIdx.x == 0) n_ids[b] = n;
 }
 
+// ---- orientation targets: join with the image's {instance id: biternion} table, paint ----------
+// OrientationTargetGenerator._preprocess (data/preprocessing/orientation.py:37-97).  The scan above
+// has decided every present id (majority class flagged, or present at all without a class list:
+// TgView.enc); a key is accepted when its id is present and decided.  Every workgroup stages the
+// image's keys, accept flags and biternions in LDS once, then walks its pixels: 4 per lane, one
+// 16-byte id load, two 16-byte stores to the channel planes and one 4-byte store of the mask bytes.
+// A lane looks an id up once per run of equal ids; id 0 (most pixels) is not looked up at all.
+//   PROBE = true   the scan's presence bitmap + prefix (two dependent loads through the L2) give
+//                  the dense rank, an LDS table [cap] maps the rank to the key: what runs
+//   PROBE = false  binary search over the ascending keys in LDS: 3 us slower per B = 32 batch of
+//                  640 x 480 (6 dependent LDS reads per lane and run, lanes diverging), kept for
+//                  the A/B of tools/bench_orientation_targets.py (NMSA_OT_LOOKUP=search)
+constexpr int OT_MAX_KEYS = 4096;
+constexpr int OT_PX = 256 * 4;               // pixels per workgroup and trip
+
+__host__ __device__ inline size_t ot_lds_bytes(int K, int cap, bool probe)
+{
+    // keys i32 [K] (or rank -> key + 1 u16 [cap]) | biternion f32 [K * 2] | accept u8 [K]
+    const size_t tab = probe ? (((size_t)cap * 2 + 7) & ~(size_t)7) : (((size_t)K * 4 + 7) & ~(size_t)7);
+    return tab + (size_t)K * 8 + (((size_t)K + 15) & ~(size_t)15);
+}
+
+template <bool FAST, bool PROBE>
+__global__ __launch_bounds__(256) void k_ot_paint(
+    const void* __restrict__ ins, int ins_dtype, const int32_t* __restrict__ keys,
+    const int32_t* __restrict__ n_keys, const float* __restrict__ biternion, int K, int P, int cap,
+    int NC, unsigned char* __restrict__ ws, float* __restrict__ orientation,
+    uint8_t* __restrict__ foreground, uint8_t* __restrict__ present)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ot_lds[];
+    const size_t tab_bytes = PROBE ? (((size_t)cap * 2 + 7) & ~(size_t)7) : (((size_t)K * 4 + 7) & ~(size_t)7);
+    int* s_key = (int*)ot_lds;                              // [K] ascending ids        (!PROBE)
+    uint16_t* s_of_rank = (uint16_t*)ot_lds;                // [cap] key + 1, 0 = none  (PROBE)
+    float2* s_bit = (float2*)(ot_lds + tab_bytes);          // [K] (cos, sin)
+    uint8_t* s_acc = (uint8_t*)(s_bit + K);                 // [K]
+    const int b = blockIdx.y;
+    TgView v = tg_view(ws, b, cap, NC);
+    const int n = max(0, min(n_keys[b], K));
+    if (PROBE) {
+        for (int d = threadIdx.x; d < cap; d += 256) s_of_rank[d] = 0;
+        __syncthreads();
+    }
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int id = k < n ? keys[(size_t)b * K + k] : 0;
+        int acc = 0, d = 0;
+        if (id > 0 && id <= MW_MAX_ID) {
+            const uint32_t w = v.bitmap[id >> 5];
+            if ((w >> (id & 31)) & 1u) {
+                d = (int)v.prefix[id >> 5] + __popc(w & ((1u << (id & 31)) - 1u));
+                acc = d < cap && v.enc[d] != 0;
+            }
+        }
+        if (PROBE) { if (acc) s_of_rank[d] = (uint16_t)(k + 1); }
+        else s_key[k] = id;
+        s_acc[k] = (uint8_t)acc;
+        s_bit[k] = acc ? *(const float2*)(biternion + ((size_t)b * K + k) * 2) : make_float2(0.f, 0.f);
+        if (blockIdx.x == 0) present[(size_t)b * K + k] = (uint8_t)acc;
+    }
+    __syncthreads();
+    // position of `id` (in [1, 65535]) among the accepted keys, -1: none
+    auto find = [&](int id) -> int {
+        if (PROBE) {
+            const uint32_t w = v.bitmap[id >> 5];
+            if (!((w >> (id & 31)) & 1u)) return -1;
+            const int d = (int)v.prefix[id >> 5] + __popc(w & ((1u << (id & 31)) - 1u));
+            return d < cap ? (int)s_of_rank[d] - 1 : -1;
+        }
+        int lo = 0, hi = n;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_key[mid] < id) lo = mid + 1; else hi = mid;
+        }
+        return (lo < n && s_key[lo] == id && s_acc[lo]) ? lo : -1;
+    };
+    float* o0 = orientation + (size_t)b * 2 * P;
+    float* o1 = o0 + P;
+    for (int p0 = (blockIdx.x * 256 + threadIdx.x) * 4; p0 < P; p0 += gridDim.x * OT_PX) {
+        const int nvalid = min(4, P - p0);
+        const size_t o = (size_t)b * P + p0;
+        int64_t id[4];
+        load_ins4<FAST>(ins, ins_dtype, o, nvalid, id);
+        float c[4], s[4];
+        uint8_t fg[4];
+        int64_t id_prev = -1;
+        float2 q_prev = make_float2(0.f, 0.f);
+        uint8_t fg_prev = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c[j] = 0.f; s[j] = 0.f; fg[j] = 0;
+            if (id[j] <= 0 || id[j] > MW_MAX_ID) continue;
+            if (id[j] != id_prev) {
+                const int k = find((int)id[j]);
+                fg_prev = k >= 0;
+                q_prev = k >= 0 ? s_bit[k] : make_float2(0.f, 0.f);
+                id_prev = id[j];
+            }
+            c[j] = q_prev.x; s[j] = q_prev.y; fg[j] = fg_prev;
+        }
+        if (FAST) {
+            typedef float f32x4_t __attribute__((ext_vector_type(4)));
+            typedef unsigned char u8x4_t __attribute__((ext_vector_type(4)));
+            f32x4_t c4, s4;
+            c4.x = c[0]; c4.y = c[1]; c4.z = c[2]; c4.w = c[3];
+            s4.x = s[0]; s4.y = s[1]; s4.z = s[2]; s4.w = s[3];
+            u8x4_t f4; f4.x = fg[0]; f4.y = fg[1]; f4.z = fg[2]; f4.w = fg[3];
+            *(f32x4_t*)(o0 + p0) = c4;
+            *(f32x4_t*)(o1 + p0) = s4;
+            *(u8x4_t*)(foreground + o) = f4;
+        } else {
+            for (int j = 0; j < nvalid; ++j) {
+                o0[p0 + j] = c[j];
+                o1[p0 + j] = s[j];
+                foreground[o + j] = fg[j];
+            }
+        }
+    }
+}
+
 int tg_cap(int max_instances) { return ((max_instances + 1023) / 1024) * 1024; }
 
 // the vectorised label loaders apply to the on-wire dtypes with 4-pixel aligned images
@@ -1832,6 +1950,69 @@ extern "C" int nmsa_panoptic_targets(const void* semantic, int sem_dtype, const 
         hipLaunchKernelGGL(k_tg_naive_paint<false>, dim3(gx, B), dim3(256), 0, stream, semantic, sem_dtype,
                            instance, ins_dtype, is_thing_class, P, cap, n_classes,
                            max_instances_per_category, void_label, ws, panoptic);
+    return check_launch();
+}
+
+extern "C" int nmsa_orientation_targets(const void* semantic, int sem_dtype, const void* instance,
+                                        int ins_dtype, const uint8_t* estimate_class,
+                                        const int32_t* keys, const int32_t* n_keys, const float* biternion,
+                                        int B, int n_classes, int H, int W, int K, int max_instances,
+                                        float* orientation, uint8_t* foreground, uint8_t* present,
+                                        int32_t* status, void* workspace, size_t workspace_bytes,
+                                        int workspace_is_clean, nmsa_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!semantic || !instance || !keys || !n_keys || !biternion || !orientation || !foreground ||
+        !present || !status || !workspace)
+        return NMSA_ERR_ARG;
+    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || H > 32767 || W > 32767 ||
+        (int64_t)H * W > ((int64_t)1 << 30))
+        return NMSA_ERR_ARG;
+    if (n_classes <= 0 || n_classes > 65536 || K <= 0 || K > OT_MAX_KEYS) return NMSA_ERR_ARG;
+    if (max_instances <= 0 || max_instances > 4096) return NMSA_ERR_ARG;
+    if (tg_bad_dtype(sem_dtype) || tg_bad_dtype(ins_dtype)) return NMSA_ERR_ARG;
+    if ((uintptr_t)keys % 4 || (uintptr_t)n_keys % 4 || (uintptr_t)biternion % 8) return NMSA_ERR_ARG;
+    const int cap = tg_cap(max_instances);
+    const size_t need = nmsa_targets_workspace_bytes(B, n_classes, max_instances);
+    if (workspace_bytes < need) return NMSA_ERR_WORKSPACE;
+    if ((uintptr_t)workspace % 8) return NMSA_ERR_ARG;
+    unsigned char* ws = (unsigned char*)workspace;
+    const int P = H * W;
+    // the vote and the decision are the instance targets' (estimate_class in the place of
+    // is_thing_class; NULL: every present id is decided); the lists of ids are not asked for
+    bool decided = false;
+    int rc = tg_common(semantic, sem_dtype, instance, ins_dtype, B, n_classes, P, W, cap, true, ws, need,
+                       status, stream, estimate_class, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                       nullptr, nullptr, nullptr, &decided, workspace_is_clean);
+    if (rc) return rc;
+    if (!decided) {
+        hipLaunchKernelGGL(k_tg_decide, dim3(B), dim3(1024), 0, stream, ws, cap, n_classes, estimate_class,
+                           (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+        if ((rc = check_launch())) return rc;
+    }
+    // the lookup: a probe of the scan's id table (54 us per call at B = 32, 640 x 480, 34 keys per
+    // image) — NMSA_OT_LOOKUP=search (read per call: same-process A/B, tools/
+    // bench_orientation_targets.py): the binary search over the keys in LDS (57 us)
+    const char* e = getenv("NMSA_OT_LOOKUP");
+    const bool probe = !(e && e[0] == 's');
+    const bool fast = ins_dtype == NMSA_I32 && P % 4 == 0 && (uintptr_t)instance % 16 == 0 &&
+                      (uintptr_t)orientation % 16 == 0 && (uintptr_t)foreground % 4 == 0;
+    // one round of resident workgroups over the batch, at most one per 1024 pixels of an image
+    const DeviceGeometry g = device_geometry();
+    const size_t lds = ot_lds_bytes(K, cap, probe);
+    long long per_cu = (long long)(g.lds_per_cu / lds);
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    long long gx = (long long)g.cus * per_cu / B;
+    if (gx > (P + OT_PX - 1) / OT_PX) gx = (P + OT_PX - 1) / OT_PX;
+    if (gx < 1) gx = 1;
+    const dim3 grid((unsigned)gx, B);
+#define NMSA_LAUNCH_OT(F, Q) do { rc = allow_dynamic_lds(k_ot_paint<F, Q>, lds); if (rc) return rc;            \
+    hipLaunchKernelGGL((k_ot_paint<F, Q>), grid, dim3(256), lds, stream, instance, ins_dtype, keys, n_keys,     \
+                       biternion, K, P, cap, n_classes, ws, orientation, foreground, present); } while (0)
+    if (fast) { if (probe) NMSA_LAUNCH_OT(true, true); else NMSA_LAUNCH_OT(true, false); }
+    else { if (probe) NMSA_LAUNCH_OT(false, true); else NMSA_LAUNCH_OT(false, false); }
+#undef NMSA_LAUNCH_OT
     return check_launch();
 }
 

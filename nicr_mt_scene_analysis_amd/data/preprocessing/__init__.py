@@ -12,4 +12,5 @@ from .resize import get_valid_region_slices_and_fullres_shape
 from .dense_visual_embedding import DenseVisualEmbeddingTargetGenerator
 from .instance import InstanceClearStuffIDs
 from .instance import InstanceTargetGenerator
+from .orientation import OrientationTargetGenerator
 from .panoptic import PanopticTargetGenerator

@@ -516,6 +516,52 @@ def panoptic_targets(
             'status': status}
 
 
+def orientation_targets(
+    semantic: torch.Tensor,
+    instance: torch.Tensor,
+    n_classes: int,
+    estimate_class: Optional[torch.Tensor],
+    keys: torch.Tensor,
+    n_keys: torch.Tensor,
+    biternion: torch.Tensor,
+    max_instances: int = 1024,
+) -> Dict[str, torch.Tensor]:
+    """reference: OrientationTargetGenerator._preprocess (data/preprocessing/orientation.py:37-97)
+    for a whole batch [B,H,W].  `keys` i32 [B,K]: per image the instance ids that have an
+    orientation, strictly ascending, the first `n_keys[b]` valid; `biternion` f32 [B,K,2] their
+    (cos, sin).  `present` u8 [B,K] flags the keys that were painted."""
+    sem = L.require_device_tensor(semantic, 'semantic')
+    ins = L.require_device_tensor(instance, 'instance')
+    k = L.require_device_tensor(keys, 'keys')
+    nk = L.require_device_tensor(n_keys, 'n_keys')
+    bit = L.require_device_tensor(biternion, 'biternion')
+    B, H, W = sem.shape
+    K = int(k.shape[1])
+    if k.dtype != torch.int32 or nk.dtype != torch.int32 or bit.dtype != torch.float32:
+        raise TypeError('keys / n_keys must be int32 and biternion float32')
+    if tuple(k.shape) != (B, K) or tuple(nk.shape) != (B,) or tuple(bit.shape) != (B, K, 2):
+        raise ValueError(f'keys [B,K], n_keys [B], biternion [B,K,2] expected for B = {B}, got '
+                         f'{tuple(k.shape)}, {tuple(nk.shape)}, {tuple(bit.shape)}')
+    dev = sem.device
+    est = None if estimate_class is None else _u8(estimate_class)
+    ori = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+    fg = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    present = torch.empty((B, K), dtype=torch.uint8, device=dev)
+    on_wire = _targets_on_wire(sem, ins, H, W, int(n_classes))
+    ws, ws_bytes, ws_entry = _targets_workspace(B, int(n_classes), int(max_instances), dev, reusable=on_wire)
+    clean, ws_entry[1] = ws_entry[1], 0
+    status = torch.empty((1,), dtype=torch.int32, device=dev) if on_wire else \
+        torch.zeros((1,), dtype=torch.int32, device=dev)
+    L.check(L.lib().nmsa_orientation_targets(
+        L.ptr(sem), L.int_dtype_code(sem), L.ptr(ins), L.int_dtype_code(ins), L.ptr(est),
+        L.ptr(k), L.ptr(nk), L.ptr(bit), B, int(n_classes), H, W, K, int(max_instances),
+        L.ptr(ori), L.ptr(fg), L.ptr(present), L.ptr(status), L.ptr(ws), ws_bytes, int(clean),
+        L.stream_ptr(dev)), 'nmsa_orientation_targets')
+    ws_entry[1] = int(on_wire)
+    return {'orientation': ori, 'foreground': fg.view(torch.bool), 'present': present,
+            'status': status}
+
+
 def dve_targets(
     panoptic: torch.Tensor,
     keys: torch.Tensor,

@@ -529,3 +529,60 @@ def make_normal_inputs(recipe: str, seed: int) -> Dict[str, np.ndarray]:
     out['target_fullres'] = _normal_target(rng, B, H, W, holes)
     out['metric_mask'] = rng.random((B, H, W)) < 0.6
     return out
+
+
+# ---- orientation targets (data/preprocessing/orientation.py) ------------------------------------
+# recipe -> (B, n_classes, H, W, random instances per image)
+ORIENTATION_RECIPES = {
+    'ragged': (3, 5, 37, 53, 8),          # W % 4 != 0: the per-pixel path
+    'wire': (3, 41, 96, 128, 12),         # the on-wire layout; one instance over half of image 0
+}
+# ids of the crafted instances of image 0 (2 x 4 pixel blocks unless noted)
+ORI_VOID, ORI_UNFLAGGED, ORI_TIE_FLAGGED, ORI_TIE_UNFLAGGED, ORI_NO_ANGLE, ORI_NOT_IN_MAP, ORI_BIG = \
+    60001, 60002, 60003, 60004, 60005, 60006, 60007
+
+
+def make_orientation_inputs(recipe: str, seed: int) -> Dict:
+    """Label maps of `make_label_maps` plus per-image {instance id: angle in rad} dicts for the
+    orientation target generator.  Odd classes are the ones whose orientation is estimated (void
+    is not).  Image 0 holds crafted instances: majority class void; majority class not flagged;
+    an exact vote tie between classes 1 (flagged) and 2 (not), which class 1 wins; a tie between
+    classes 2 and 3, which class 2 wins; an instance without an angle; an angle for an id that is
+    not in the map; and (maps of 96 rows or more) one instance over the upper 60 rows, whose vote
+    is spread over several workgroups.  Image 1 has angles for about two thirds of its random
+    instances, image 2 an empty dict.  The angles include 0, pi, a negative one and one above 2 pi."""
+    B, C, H, W, n_inst = ORIENTATION_RECIPES[recipe]
+    maps = make_label_maps(B, C, H, W, n_instances=n_inst, seed=seed)
+    sem, ins = maps['semantic'], maps['instance']
+    rng = np.random.default_rng(seed + 7919)
+    assert not np.isin(ins, np.arange(ORI_VOID, ORI_BIG + 1)).any()
+    if H >= 96:
+        ins[0, :60, :] = ORI_BIG
+
+    def block(y, x, iid, left, right):
+        ins[0, y:y + 2, x:x + 4] = iid
+        sem[0, y:y + 2, x:x + 2] = left
+        sem[0, y:y + 2, x + 2:x + 4] = right
+
+    block(1, 1, ORI_VOID, 0, 0)
+    block(1, 8, ORI_UNFLAGGED, 2, 2)
+    block(5, 1, ORI_TIE_FLAGGED, 2, 1)
+    block(5, 8, ORI_TIE_UNFLAGGED, 3, 2)
+    block(9, 1, ORI_NO_ANGLE, 1, 1)
+    orientations = []
+    for b in range(B):
+        d = {}
+        if b < 2:
+            for iid in np.unique(ins[b]):
+                if iid != 0 and iid < ORI_VOID and rng.random() < 0.67:
+                    d[int(iid)] = float(rng.uniform(-np.pi, 3.0 * np.pi))
+        if b == 0:
+            d.update({ORI_VOID: 0.0, ORI_UNFLAGGED: float(np.pi), ORI_TIE_FLAGGED: -1.25,
+                      ORI_TIE_UNFLAGGED: 7.0, ORI_NOT_IN_MAP: 1.0})
+            if H >= 96:
+                d[ORI_BIG] = 2.5
+        if b == 1:
+            d[int(ins[b].max()) + 1] = 0.5                  # an angle without an instance
+        orientations.append(d)
+    return {'semantic': sem, 'instance': ins, 'estimate': np.arange(C) % 2 == 1,
+            'orientations': orientations}
