@@ -823,6 +823,63 @@ int nmsa_rmse_update(const void* pred, int pred_dtype, const float* target, cons
                      int Hs, int Ws, int y0, int x0, int h, int w,
                      double* sum_state, int64_t* count_state, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * orientation MAE on device tables (csrc/maae.hip)
+ *
+ * An ORIENTATION TABLE holds, per image, {integer key: angle in rad}:
+ *   keys   i32 [B,K] ascending within the first n[b] columns, or NULL for a dense table (key =
+ *          column index, every column looked at; n may then be NULL too)
+ *   angle  f32 [B,K], valid u8 [B,K] (0: the column is no entry), n i32 [B], K > 0
+ *   status i32 [1] or NULL: the status word of nmsa_instance_orientation_wide when that call made
+ *          the table; its bits 1 / 32 are OR-ed into `status` as NMSA_ST_MAAE_WIDE_OVERFLOW /
+ *          NMSA_ST_MAAE_WIDE_RANGE
+ * An ID TABLE holds, per image, {panoptic id: instance id}: pan i64 [B,K], ins i64 [B,K], n i32 [B];
+ *   `ascending` != 0 promises ascending pan rows (binary search), 0 makes every lookup walk the row
+ *   (the tables of the merge kernels are in insertion order).
+ *
+ * nmsa_maae_update_keyed: MeanAbsoluteAngularError.update, metric/mae.py:40-64.  For every valid
+ *   key of the prediction table the target angle under the same key of the same image is looked
+ *   up; a key the target lacks (KeyError in the reference) raises NMSA_ST_MAAE_MISSING_TARGET and
+ *   the pair is skipped.
+ * nmsa_maae_update_matched: PanopticQualityWithOrientationMAE.update_mae, metric/mae.py:129-162, on
+ *   the match table of nmsa_pq_update (matches i64 [B,match_capacity,2] (target id, pred id),
+ *   n_matches i32 [B]).  Target id 0 is skipped; target id -> target instance -> target angle, then
+ *   pred id -> pred instance -> pred angle; a pair counts when all four lookups hit.
+ *   n_matches[b] > match_capacity raises NMSA_ST_MAAE_MATCH_OVERFLOW and the image contributes its
+ *   first match_capacity rows.
+ *
+ * Both add to *sum_state (f64) the |angle error| of every counted pair and to *count_state (i64)
+ * their number: DEVICE pointers into the metric's states.  The error is the float32 chain
+ *   rem(x, m) = fmodf(x, m), plus m when the result is non-zero and negative
+ *   e = fabsf(rem((rem(p, m) - rem(t, m)) + pi, m) - pi),  m = (float)(2 pi), pi = (float)M_PI
+ * every step IEEE-rounded, e widened to f64.  One workgroup, fixed reduction order: two runs on the
+ * same input give bit-identical states.  No workspace, no host sync; capturable in a hipGraph, a
+ * replay adds again.  NMSA_ERR_ARG: NULL / non-positive arguments.
+ * ------------------------------------------------------------------------- */
+#define NMSA_ST_MAAE_MISSING_TARGET 64
+#define NMSA_ST_MAAE_MATCH_OVERFLOW 128
+#define NMSA_ST_MAAE_WIDE_OVERFLOW 256
+#define NMSA_ST_MAAE_WIDE_RANGE 512
+int nmsa_maae_update_keyed(const int32_t* pred_keys, const float* pred_angle, const uint8_t* pred_valid,
+                           const int32_t* pred_n, int pred_K, const int32_t* pred_status,
+                           const int32_t* target_keys, const float* target_angle,
+                           const uint8_t* target_valid, const int32_t* target_n, int target_K,
+                           const int32_t* target_status,
+                           int B, double* sum_state, int64_t* count_state, int32_t* status,
+                           nmsa_stream_t stream);
+int nmsa_maae_update_matched(const int64_t* matches, const int32_t* n_matches, int match_capacity,
+                             const int64_t* pred_ids_pan, const int64_t* pred_ids_ins,
+                             const int32_t* pred_ids_n, int pred_ids_K, int pred_ids_ascending,
+                             const int32_t* pred_keys, const float* pred_angle, const uint8_t* pred_valid,
+                             const int32_t* pred_n, int pred_K, const int32_t* pred_status,
+                             const int64_t* target_ids_pan, const int64_t* target_ids_ins,
+                             const int32_t* target_ids_n, int target_ids_K, int target_ids_ascending,
+                             const int32_t* target_keys, const float* target_angle,
+                             const uint8_t* target_valid, const int32_t* target_n, int target_K,
+                             const int32_t* target_status,
+                             int B, double* sum_state, int64_t* count_state, int32_t* status,
+                             nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

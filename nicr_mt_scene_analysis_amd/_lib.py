@@ -89,6 +89,12 @@ _SIGNATURES = {
     'nmsa_normal_valid_mask': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'nmsa_rmse_update': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                               _vp, _vp, _vp]),
+    # an orientation table is (keys, angle, valid, n, K, status), an id table (pan, ins, n, K, ascending)
+    'nmsa_maae_update_keyed': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                    _i, _vp, _vp, _vp, _vp]),
+    'nmsa_maae_update_matched': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp,
+                                      _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp,
+                                      _i, _vp, _vp, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -1,17 +1,39 @@
 """Orientation MAE on matched instances (reference metric/mae.py:15-172).
 
-The PQ part runs on the device; the per-matched-pair angle bookkeeping works on
-Python dicts of <= a few dozen floats per image and stays on the host
-("MAAE scalars stay host-side")."""
+The PQ part runs on the device.  The per-pair angle bookkeeping has two forms.  Handed
+`utils.OrientationTable` / `utils.IdTable` objects in every orientation and id argument, the join
+and the angle errors run on the device too (csrc/maae.hip: `nmsa_maae_update_keyed`,
+`nmsa_maae_update_matched`, fed with the match table of `nmsa_pq_update` as it lies on the
+device): no device->host copy, graph-capturable, what the reference raises in `update` (KeyError,
+ValueError) arrives at `compute()` through the status word.  Handed lists of dicts, or a mixture
+(tables are then turned into dicts), the reference's host loop runs on one copy of the match
+counts and one of the match table per update."""
 import math
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 
+from .. import ops
+from ..utils._tables import IdTable
+from ..utils._tables import OrientationTable
 from .base import Metric
 from .pq import PanopticQuality
+from .pq import _STATUS_MESSAGES as _PQ_STATUS_MESSAGES
 
 OrientationDict = Dict[int, float]
+Orientations = Union[List[OrientationDict], OrientationTable]
+Ids = Union[List[Dict], IdTable]
+
+_MAE_STATUS_MESSAGES = {
+    64: 'an orientation key of the prediction is missing in the target (the reference raises KeyError)',
+    128: 'more matched segments per image than the match table holds',
+    256: 'more than 4096 distinct instance ids in one image',
+    512: 'instance ids outside [0, 65535] are not supported (dataset instance maps are uint16)',
+}
+
+
+def _as_dicts(x):
+    return x.to_dicts() if isinstance(x, (OrientationTable, IdTable)) else x
 
 
 def abs_angle_error_rad(pred_angle: torch.Tensor, target_angle: torch.Tensor) -> torch.Tensor:
@@ -50,14 +72,39 @@ class MeanAbsoluteAngularError(_AngularErrorStates, Metric):
     def __init__(self, **kwargs) -> None:
         super().__init__(**kwargs)
         self._add_angular_states()
+        self._status = torch.zeros((1,), dtype=torch.int32, device=self.device)
 
-    def update(self, orientation_preds: List[OrientationDict],
-               orientation_target: List[OrientationDict]) -> None:
+    def to(self, device, *args, **kwargs):
+        super().to(device)
+        self._status = self._status.to(self.device)
+        return self
+
+    def reset(self) -> None:
+        super().reset()
+        if hasattr(self, '_status'):
+            self._status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+
+    def update(self, orientation_preds: Orientations, orientation_target: Orientations) -> None:
+        if isinstance(orientation_preds, OrientationTable) and \
+                isinstance(orientation_target, OrientationTable):
+            self._pack()                                    # the states as views of the flat buffers
+            ops.maae_update_keyed(self.sum_angular_error, self.n_elements, self._status,
+                                  orientation_preds, orientation_target)
+            return
+        orientation_preds, orientation_target = _as_dicts(orientation_preds), _as_dicts(orientation_target)
         self._accumulate((angle, targets[key])
                          for preds, targets in zip(orientation_preds, orientation_target)
                          for key, angle in preds.items())
 
+    def _check_status(self) -> None:
+        st = int(self._status.item())
+        if st:
+            self._status.zero_()
+            msgs = [m for bit, m in _MAE_STATUS_MESSAGES.items() if st & bit]
+            raise ValueError('MeanAbsoluteAngularError: ' + '; '.join(msgs))
+
     def compute(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        self._check_status()
         rad = self._mean_rad()
         return rad, torch.rad2deg(rad)
 
@@ -69,11 +116,11 @@ class PanopticQualityWithOrientationMAE(_AngularErrorStates, PanopticQuality):
 
     def update(self,
                panoptic_preds: torch.Tensor,
-               orientation_preds: Optional[List[OrientationDict]],
-               panoptic_preds_id_dicts: Optional[List[Dict]],
+               orientation_preds: Optional[Orientations],
+               panoptic_preds_id_dicts: Optional[Ids],
                panoptic_target: torch.Tensor,
-               orientation_target: Optional[List[OrientationDict]],
-               panoptic_target_id_dicts: Optional[List[Dict]],
+               orientation_target: Optional[Orientations],
+               panoptic_target_id_dicts: Optional[Ids],
                miou=None, semantic_target: Optional[torch.Tensor] = None,
                pred_div: int = 1, panoptic_pred_parts: Optional[dict] = None) -> None:
         """`miou` / `semantic_target` / `pred_div` (extension): also do
@@ -98,6 +145,19 @@ class PanopticQualityWithOrientationMAE(_AngularErrorStates, PanopticQuality):
         if not with_mae:
             return
         matches, n_matches = res
+        if isinstance(orientation_preds, OrientationTable) and \
+                isinstance(orientation_target, OrientationTable) and \
+                isinstance(panoptic_preds_id_dicts, IdTable) and \
+                isinstance(panoptic_target_id_dicts, IdTable):
+            # the match table goes into the join as it lies on the device: nothing is copied
+            self._pack()
+            ops.maae_update_matched(self.sum_angular_error, self.n_elements, self._status,
+                                    matches, n_matches, panoptic_preds_id_dicts, orientation_preds,
+                                    panoptic_target_id_dicts, orientation_target)
+            return
+        orientation_preds, orientation_target = _as_dicts(orientation_preds), _as_dicts(orientation_target)
+        panoptic_preds_id_dicts = _as_dicts(panoptic_preds_id_dicts)
+        panoptic_target_id_dicts = _as_dicts(panoptic_target_id_dicts)
         # match counts and the status word in one copy (the sync of this update)
         head = torch.cat([n_matches, self._status]).cpu().tolist()
         n_host, status = head[:-1], head[-1]
@@ -130,6 +190,13 @@ class PanopticQualityWithOrientationMAE(_AngularErrorStates, PanopticQuality):
             if target_angle is not None and pred_angle is not None:
                 pairs.append((pred_angle, target_angle))
         self._accumulate(pairs)
+
+    def _check_status(self) -> None:
+        st = int(self._status.item())
+        if st:
+            self._status.zero_()
+            msgs = [m for bit, m in {**_PQ_STATUS_MESSAGES, **_MAE_STATUS_MESSAGES}.items() if st & bit]
+            raise ValueError('PanopticQuality: ' + '; '.join(msgs))
 
     def compute(self, suffix: str = '') -> Dict[str, torch.Tensor]:
         r = super().compute(suffix=suffix)

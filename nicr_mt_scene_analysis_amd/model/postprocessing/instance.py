@@ -20,6 +20,8 @@ from ...data.preprocessing.resize import get_valid_region_slices_and_fullres_sha
 from ...types import BatchType
 from ...types import DecoderRawOutputType
 from ...types import PostprocessingOutputType
+from ...utils._tables import OrientationTable
+from ._lazy import LazyDict
 from .dense_base import DensePostprocessingBase
 
 
@@ -141,56 +143,49 @@ class InstancePostprocessing(DensePostprocessingBase):
         return self._segment(center_heatmap, center_offset, foreground_mask, 1.0, 1.0)
 
     # -------------------------------------------------------------- orientation
-    def _get_instance_orientation(
+    def _get_instance_orientation_table(
         self,
         orientation: torch.Tensor,
         instance_segmentation: torch.Tensor,
         foreground_mask: Optional[torch.Tensor]
-    ) -> List[Dict[int, float]]:
+    ) -> OrientationTable:
+        """{instance id: angle} per image as a device table (extension): the sums kernels and
+        `torch.atan2` on the device, no device->host copy.  uint8 / bool maps (predictions) give a
+        dense table (key = column), wider maps (ground truth) a keyed one."""
         seg = instance_segmentation
         if seg.ndim == 4:
             seg = seg[:, 0]
         if seg.dtype == torch.bool:
             seg = seg.view(torch.uint8)
         if seg.dtype != torch.uint8:
-            return self._get_instance_orientation_wide(orientation, seg, foreground_mask)
+            return self._get_instance_orientation_table_wide(orientation, seg, foreground_mask)
         r = ops.instance_orientation_sums(orientation, seg.contiguous(), foreground_mask)
         sums = r['sums'].to(torch.float32)
         # angle = atan2(sum(sin), sum(cos))  (utils/_orientation.py:39-42)
         angle = torch.atan2(sums[..., 1], sums[..., 0])
-        packed = torch.cat([angle.to(torch.float64), r['count'].to(torch.float64)], dim=1).cpu().tolist()
-        out = []
-        for row in packed:
-            out.append({i: row[i] for i in range(1, 256) if row[256 + i] > 0})
-        return out
+        valid = (r['count'] > 0).to(torch.uint8)
+        valid[:, 0] = 0                                   # id 0 is "no instance"
+        return OrientationTable(None, angle, valid, None)
 
-    def _get_instance_orientation_wide(self, orientation, seg, foreground_mask):
+    def _get_instance_orientation_table_wide(self, orientation, seg, foreground_mask):
         """ground-truth instance maps (uint16 ids stored as int32 / int64, instance.py:432-438):
-        ids are ranked on the device, the dict is keyed by the original ids"""
-        max_instances = 1024
-        while True:
-            r = ops.instance_orientation_sums_wide(orientation, seg.contiguous(), foreground_mask,
-                                                   max_instances)
-            head = torch.cat([r['status'], r['n_ids']]).cpu().tolist()
-            if head[0] & 1 and max_instances < 4096:
-                max_instances = 4096
-                continue
-            break
-        if head[0] & 32:
-            raise NotImplementedError('instance ids outside [0, 65535] are not supported '
-                                      '(dataset instance maps are uint16)')
-        if head[0] & 1:
-            raise NotImplementedError('more than 4096 distinct instance ids in one image')
-        nmax = max(1, max(head[1:]))
-        sums = r['sums'][:, :nmax].to(torch.float32)
+        ids are ranked on the device, the table is keyed by the original ids.  One run with the
+        largest id table the kernel has (4096); its status word travels with the table."""
+        r = ops.instance_orientation_sums_wide(orientation, seg.contiguous(), foreground_mask, 4096)
+        sums = r['sums'].to(torch.float32)
         angle = torch.atan2(sums[..., 1], sums[..., 0])
-        packed = torch.cat([r['ids'][:, :nmax].to(torch.float64), angle.to(torch.float64),
-                            r['count'][:, :nmax].to(torch.float64)], dim=1).cpu().tolist()
-        out = []
-        for b, row in enumerate(packed):
-            n = head[1 + b]
-            out.append({int(row[i]): row[nmax + i] for i in range(n) if row[2 * nmax + i] > 0})
-        return out
+        return OrientationTable(r['ids'], angle, (r['count'] > 0).to(torch.uint8), r['n_ids'],
+                                status=r['status'])
+
+    def _get_instance_orientation(
+        self,
+        orientation: torch.Tensor,
+        instance_segmentation: torch.Tensor,
+        foreground_mask: Optional[torch.Tensor]
+    ) -> List[Dict[int, float]]:
+        """ONE device->host copy; too many ids / ids out of range raise here"""
+        return self._get_instance_orientation_table(orientation, instance_segmentation,
+                                                    foreground_mask).to_dicts()
 
     # ---------------------------------------------------------------- interface
     def _postprocess_training(
@@ -221,12 +216,12 @@ class InstancePostprocessing(DensePostprocessingBase):
         else:
             center_heatmap, center_offset = output
 
-        r = {
+        r = LazyDict({
             'instance_output': output,
             'instance_side_outputs': side_outputs,
             'instance_centers': center_heatmap,
             'instance_offsets': center_offset,
-        }
+        })
         if with_orientation:
             r['instance_orientation'] = orientation
 
@@ -258,16 +253,23 @@ class InstancePostprocessing(DensePostprocessingBase):
         if not with_orientation:
             return r
 
-        # o-1 / o-2 (instance.py:432-449), o-3 / o-4 debugging (:451-466)
+        # o-1 / o-2 (instance.py:432-449), o-3 / o-4 debugging (:451-466).  o-1 / o-2 are built when
+        # read: as device tables under aux['orientation_tables'] (what the task helpers take), as
+        # the reference's lists of dicts under the public keys
+        tables = r.aux['orientation_tables'] = LazyDict()
+
+        def _publish(key, seg, fg):
+            tables.set_lazy(key, lambda: self._get_instance_orientation_table(orientation, seg, fg))
+            r.set_derived(key, lambda d, k=key: d.aux['orientation_tables'][k].to_dicts())
+
         if all(k in batch for k in ('instance', 'orientation_foreground')):
-            r['orientations_gt_instance_gt_orientation_foreground'] = \
-                self._get_instance_orientation(orientation, batch['instance'].to(orientation.device),
-                                               batch['orientation_foreground'].to(orientation.device))
+            _publish('orientations_gt_instance_gt_orientation_foreground',
+                     batch['instance'].to(orientation.device),
+                     batch['orientation_foreground'].to(orientation.device))
         if all(k in batch for k in ('instance_foreground', 'orientation_foreground')):
-            r['orientations_instance_segmentation_gt_orientation_foreground'] = \
-                self._get_instance_orientation(orientation,
-                                               r['instance_segmentation_gt_foreground'],
-                                               batch['orientation_foreground'].to(orientation.device))
+            _publish('orientations_instance_segmentation_gt_orientation_foreground',
+                     r['instance_segmentation_gt_foreground'],
+                     batch['orientation_foreground'].to(orientation.device))
         if self.debug:
             r['orientations_gt_instance'] = self._get_instance_orientation(
                 orientation, batch['instance'].to(orientation.device), None)

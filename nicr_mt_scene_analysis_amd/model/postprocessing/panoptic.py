@@ -22,6 +22,7 @@ from ...data.preprocessing.resize import get_valid_region_slices_and_fullres_sha
 from ...types import BatchType
 from ...types import DecoderRawOutputType
 from ...types import PostprocessingOutputType
+from ...utils._tables import IdTable
 from ._lazy import LazyDict
 from .dense_base import DensePostprocessingBase
 from .instance import InstancePostprocessing
@@ -192,6 +193,7 @@ class PanopticPostprocessing(DensePostprocessingBase):
                       lambda d: torch.div(d['panoptic_segmentation_deeplab'], max_inst,
                                           rounding_mode='floor'))
         r['panoptic_segmentation_deeplab_instance_idx'] = instance_seg
+        r.aux['panoptic_id_table'] = IdTable.from_merge(p)         # the id dicts as a device table
         ori_key = 'orientations_panoptic_segmentation_deeplab_instance'
 
         def _meta(d):
@@ -205,10 +207,13 @@ class PanopticPostprocessing(DensePostprocessingBase):
             return meta
         r.set_derived('panoptic_segmentation_deeplab_instance_meta', _meta)
         if with_orientation:                      # panoptic.py:294-304, built when read
-            def _orientation(d):
-                fg = ori_lut[d['panoptic_segmentation_deeplab_semantic_idx']].to(torch.bool)
-                return post._get_instance_orientation(orientation, instance_seg, fg)
-            r.set_derived(ori_key, _orientation)
+            # as a device table under aux['orientation_tables'] (task_helper/panoptic.py joins it
+            # on the device), as the list of dicts under the public key; both built when read
+            def _orientation_table():
+                fg = ori_lut[torch.div(panoptic_seg, max_inst, rounding_mode='floor')].to(torch.bool)
+                return post._get_instance_orientation_table(orientation, instance_seg, fg)
+            r.aux.setdefault('orientation_tables', LazyDict()).set_lazy(ori_key, _orientation_table)
+            r.set_derived(ori_key, lambda d: d.aux['orientation_tables'][ori_key].to_dicts())
 
         if self._compute_scores:
             self._add_scores(r, p, r['panoptic_segmentation_deeplab_ids'],

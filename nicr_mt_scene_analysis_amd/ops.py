@@ -722,6 +722,80 @@ def rmse_update(sum_state: torch.Tensor, count_state: torch.Tensor, preds: torch
         L.ptr(sum_state), L.ptr(count_state), L.stream_ptr(t.device)), 'nmsa_rmse_update')
 
 
+# ------------------------------------------------------------- orientation MAE on device tables
+def _orientation_table_args(table, name: str, B: int) -> tuple:
+    """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""
+    if table.batch_size != B:
+        raise ValueError(f'{name} holds {table.batch_size} images, expected {B}')
+    tensors = [table.keys, table.angle, table.valid, table.n, table.status]
+    for t in tensors:
+        if t is not None:
+            _require_on_device(t, name)
+    keys, angle, valid, n, status = (None if t is None else t.contiguous() for t in tensors)
+    held = (keys, angle, valid, n, status)
+    return held, (L.ptr(keys), L.ptr(angle), L.ptr(valid), L.ptr(n), int(angle.shape[1]), L.ptr(status))
+
+
+def _id_table_args(table, name: str, B: int) -> tuple:
+    if table.batch_size != B:
+        raise ValueError(f'{name} holds {table.batch_size} images, expected {B}')
+    for t in (table.pan, table.ins, table.n):
+        _require_on_device(t, name)
+    pan, ins, n = table.pan.contiguous(), table.ins.contiguous(), table.n.contiguous()
+    return (pan, ins, n), (L.ptr(pan), L.ptr(ins), L.ptr(n), int(pan.shape[1]), int(table.ascending))
+
+
+def _maae_states(sum_state, count_state, status) -> None:
+    for name, t in (('sum_state', sum_state), ('count_state', count_state), ('status', status)):
+        _require_on_device(t, name)
+    if sum_state.dtype != torch.float64 or count_state.dtype != torch.int64 or \
+            status.dtype != torch.int32 or sum_state.numel() != 1 or count_state.numel() != 1:
+        raise TypeError('the states are one float64 and one int64 element, the status an int32 word')
+
+
+def maae_update_keyed(sum_state: torch.Tensor, count_state: torch.Tensor, status: torch.Tensor,
+                      preds, target) -> None:
+    """reference: `MeanAbsoluteAngularError.update` (metric/mae.py:40-64) on two
+    `utils.OrientationTable`s, into the metric's device states: no host sync.  A prediction key
+    the target lacks raises status bit 64 (the reference's KeyError) and is skipped."""
+    _maae_states(sum_state, count_state, status)
+    B = preds.batch_size
+    if B == 0:
+        return
+    held_p, args_p = _orientation_table_args(preds, 'preds', B)
+    held_t, args_t = _orientation_table_args(target, 'target', B)
+    L.check(L.lib().nmsa_maae_update_keyed(
+        *args_p, *args_t, B, L.ptr(sum_state), L.ptr(count_state), L.ptr(status),
+        L.stream_ptr(sum_state.device)), 'nmsa_maae_update_keyed')
+
+
+def maae_update_matched(sum_state: torch.Tensor, count_state: torch.Tensor, status: torch.Tensor,
+                        matches: torch.Tensor, n_matches: torch.Tensor,
+                        pred_ids, preds, target_ids, target) -> None:
+    """reference: `PanopticQualityWithOrientationMAE.update_mae` (metric/mae.py:129-162) for every
+    image of a batch: `matches` i64 [B,cap,2] / `n_matches` i32 [B] as `nmsa_pq_update` leaves
+    them, `utils.IdTable`s and `utils.OrientationTable`s of both sides.  More matches than `cap`
+    raise status bit 128; the image then contributes its first `cap` rows."""
+    _maae_states(sum_state, count_state, status)
+    _require_on_device(matches, 'matches')
+    _require_on_device(n_matches, 'n_matches')
+    if matches.dtype != torch.int64 or n_matches.dtype != torch.int32 or matches.ndim != 3 or \
+            matches.shape[2] != 2 or n_matches.shape != matches.shape[:1]:
+        raise TypeError('matches is int64 [B, cap, 2], n_matches int32 [B]')
+    B, cap = int(matches.shape[0]), int(matches.shape[1])
+    if B == 0:
+        return
+    m, nm = matches.contiguous(), n_matches.contiguous()
+    held_pi, args_pi = _id_table_args(pred_ids, 'pred_ids', B)
+    held_p, args_p = _orientation_table_args(preds, 'preds', B)
+    held_ti, args_ti = _id_table_args(target_ids, 'target_ids', B)
+    held_t, args_t = _orientation_table_args(target, 'target', B)
+    L.check(L.lib().nmsa_maae_update_matched(
+        L.ptr(m), L.ptr(nm), cap, *args_pi, *args_p, *args_ti, *args_t, B,
+        L.ptr(sum_state), L.ptr(count_state), L.ptr(status), L.stream_ptr(sum_state.device)),
+        'nmsa_maae_update_matched')
+
+
 # ----------------------------------------------------------------------------- a5
 def panoptic_merge(
     semantic: torch.Tensor,

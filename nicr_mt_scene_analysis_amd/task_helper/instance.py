@@ -19,6 +19,8 @@ from ..loss import VonMisesLossBiternion
 from ..metric.mae import MeanAbsoluteAngularError
 from ..metric.mae import PanopticQualityWithOrientationMAE
 from ..types import BatchType
+from ..utils._tables import IdTable
+from ..utils._tables import OrientationTable
 from ..utils.panoptic_merge import _ids_to_dicts
 from ..utils.panoptic_merge import _merge_on_device
 from .base import TaskHelperBase
@@ -29,6 +31,9 @@ KNOWN_INSTANCE_CENTER_LOSS_FUNCTIONS = ('mse', 'l1', 'focal')    # 'focal': exte
 
 
 class InstanceTaskHelper(TaskHelperBase):
+    # False: the orientation metrics always walk Python dicts on the host (same-build A/B runs)
+    use_orientation_tables = True
+
     def __init__(
         self,
         semantic_n_classes: int,
@@ -124,11 +129,23 @@ class InstanceTaskHelper(TaskHelperBase):
     @append_detached_losses_to_logs()
     def validation_step(self, batch, batch_idx, predictions_post):
         loss_dict = self._compute_losses(batch, batch_idx, predictions_post)
-        if self._with_orientation:
-            orientations_results = \
-                predictions_post['orientations_instance_segmentation_gt_orientation_foreground']
-            orientations_full_gt = \
-                predictions_post['orientations_gt_instance_gt_orientation_foreground']
+        dev = self._mae_pq_deeplab.device
+        # the orientations as device tables when the postprocessing hands them out (aux): the
+        # metrics then join them on the device and this step copies nothing to the host; results
+        # from elsewhere (plain dicts) take the reference's host loops
+        tables = getattr(predictions_post, 'aux', {}).get('orientation_tables') \
+            if self.use_orientation_tables else None
+        key_results = 'orientations_instance_segmentation_gt_orientation_foreground'
+        key_full_gt = 'orientations_gt_instance_gt_orientation_foreground'
+        on_device = self._with_orientation and dev.type == 'cuda' and tables is not None \
+            and key_results in tables and key_full_gt in tables
+        if self._with_orientation and on_device:
+            orientations_results = tables[key_results]
+            orientations_targets = OrientationTable.from_dicts(batch['orientations_present'], dev)
+            self._mae_gt.update(tables[key_full_gt], orientations_targets)
+        elif self._with_orientation:
+            orientations_results = predictions_post[key_results]
+            orientations_full_gt = predictions_post[key_full_gt]
             orientations_targets = batch['orientations_present']
             self._mae_gt.update(orientations_full_gt, orientations_targets)
         else:
@@ -136,7 +153,6 @@ class InstanceTaskHelper(TaskHelperBase):
             orientations_targets = None
 
         # instance quality with GT semantics and GT foreground (instance.py:313-357)
-        dev = self._mae_pq_deeplab.device
         semantic_batch = get_fullres(batch, 'semantic').to(dev)
         instance_batch = get_fullres(batch, 'instance').to(dev)
         instance_result = predictions_post[
@@ -150,8 +166,12 @@ class InstanceTaskHelper(TaskHelperBase):
                                   self._max_instances_per_category, self._thing_ids, 0,
                                   n_classes=self._semantic_n_classes)
         panoptic_preds = merged['panoptic']
-        panoptic_id_dicts = _ids_to_dicts(merged['ids_pan'], merged['ids_ins'], merged['n_ids']) \
-            if self._with_orientation else None
+        if on_device:
+            panoptic_id_dicts = IdTable.from_merge(merged)
+            panoptic_targets_id_dicts = IdTable.from_dicts(panoptic_targets_id_dicts, dev)
+        else:
+            panoptic_id_dicts = _ids_to_dicts(merged['ids_pan'], merged['ids_ins'], merged['n_ids']) \
+                if self._with_orientation else None
         self._mae_pq_deeplab.update(panoptic_preds, orientations_results, panoptic_id_dicts,
                                     panoptic_targets, orientations_targets,
                                     panoptic_targets_id_dicts)

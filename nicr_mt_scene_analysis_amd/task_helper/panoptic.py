@@ -11,11 +11,16 @@ from ..data.preprocessing.resize import get_fullres_key
 from ..metric import MeanIntersectionOverUnion
 from ..metric.mae import PanopticQualityWithOrientationMAE
 from ..types import BatchType
+from ..utils._tables import IdTable
+from ..utils._tables import OrientationTable
 from .base import TaskHelperBase
 from .base import append_profile_to_logs
 
 
 class PanopticTaskHelper(TaskHelperBase):
+    # False: the orientation metric always walks Python dicts on the host (same-build A/B runs)
+    use_orientation_tables = True
+
     def __init__(
         self,
         semantic_n_classes: int,                 # with void!
@@ -49,9 +54,21 @@ class PanopticTaskHelper(TaskHelperBase):
     @append_profile_to_logs('panoptic_step_time')
     def validation_step(self, batch, batch_idx, predictions_post):
         self._with_orientation = 'orientations_present' in batch
-        if self._with_orientation:
-            orientations_results = \
-                predictions_post['orientations_panoptic_segmentation_deeplab_instance']
+        target_id_dicts = batch.get('panoptic_ids_to_instance_dict')
+        aux = getattr(predictions_post, 'aux', {}) if self.use_orientation_tables else {}
+        ori_key = 'orientations_panoptic_segmentation_deeplab_instance'
+        dev = self._mae_pq_deeplab.device
+        if self._with_orientation and dev.type == 'cuda' and target_id_dicts is not None \
+                and 'panoptic_id_table' in aux and ori_key in aux.get('orientation_tables', {}):
+            # device tables from the postprocessing: the metric joins them with its match table on
+            # the device, nothing is copied to the host (results from elsewhere, without `aux`,
+            # take the dict path below)
+            orientations_results = aux['orientation_tables'][ori_key]
+            pred_id_dicts = aux['panoptic_id_table']
+            orientations_targets = OrientationTable.from_dicts(batch['orientations_present'], dev)
+            target_id_dicts = IdTable.from_dicts(target_id_dicts, dev)
+        elif self._with_orientation:
+            orientations_results = predictions_post[ori_key]
             orientations_targets = batch['orientations_present']
             # only the orientation matching walks the id dicts (lazy entry: built when read)
             pred_id_dicts = predictions_post['panoptic_segmentation_deeplab_ids']
@@ -68,7 +85,7 @@ class PanopticTaskHelper(TaskHelperBase):
             panoptic_preds_id_dicts=pred_id_dicts,
             panoptic_target=panoptic_targets,
             orientation_target=orientations_targets,
-            panoptic_target_id_dicts=batch.get('panoptic_ids_to_instance_dict'),
+            panoptic_target_id_dicts=target_id_dicts,
             # merging may change classes: mIoU of panoptic // max_instances (panoptic.py:120-126)
             # rides on the PQ pass over the prediction (one read of the i64 map for both metrics)
             miou=self._metric_iou, semantic_target=get_fullres(batch, 'semantic'),
