@@ -880,6 +880,43 @@ int nmsa_maae_update_matched(const int64_t* matches, const int32_t* n_matches, i
                              int B, double* sum_state, int64_t* count_state, int32_t* status,
                              nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * side-output targets (csrc/multiscale.hip)
+ *
+ * nmsa_multiscale_nearest: MultiscaleSupervisionGenerator._preprocess
+ *   (data/preprocessing/multiscale_supervision.py:41-67) -> resize() with cv2.INTER_NEAREST
+ *   (data/preprocessing/resize.py:95-161), for every key and every downscale of a batch in ONE
+ *   launch: per descriptor, dst[p, y, x] = src[p, maps[row_map + y], maps[col_map + x]].
+ *   staging_host   PINNED host memory, n_words 32-bit words, 8-byte aligned: n_desc descriptors
+ *                  (16 words each) followed by the concatenated i32 index maps.  The maps are the
+ *                  caller's: OpenCV's nearest rule evaluated on the host in double arithmetic.
+ *   staging_device device memory of the same size; the call enqueues ONE asynchronous copy of the
+ *                  staging buffer and the launch.  `block_begin` of every descriptor is written by
+ *                  the call (into staging_host) before the copy.
+ *   Elements move as raw bits of 1 << log2_size bytes (1, 2, 4, 8): no conversion of any kind.
+ *   Every field and every map entry is checked on the host copy before anything is enqueued:
+ *   NMSA_ERR_ARG for NULL / non-positive fields, a log2_size outside 0..3, misaligned pointers,
+ *   map offsets outside the buffer, a map entry outside [0, H) / [0, W), planes * h * w above
+ *   2^31 - 1, n_desc above NMSA_MULTISCALE_MAX_DESC.  No workspace, no host synchronisation;
+ *   capturable in a hipGraph (a replay copies the pinned buffer again: a captured call needs a
+ *   staging buffer that no later call rewrites).
+ * ------------------------------------------------------------------------- */
+#define NMSA_MULTISCALE_MAX_DESC 1024
+typedef struct nmsa_multiscale_desc {
+    uint64_t src;         /* device address of the source, [planes, H, W]                     */
+    uint64_t dst;         /* device address of the destination, [planes, h, w]                */
+    int32_t planes;       /* leading planes B * C                                             */
+    int32_t H, W;         /* source side lengths                                              */
+    int32_t h, w;         /* destination side lengths                                         */
+    int32_t log2_size;    /* log2 of the element size in bytes                                */
+    int32_t row_map;      /* word offset of the h row indices within the maps                 */
+    int32_t col_map;      /* word offset of the w column indices within the maps              */
+    int32_t block_begin;  /* first workgroup of this descriptor: written by the call          */
+    int32_t reserved[3];
+} nmsa_multiscale_desc;
+int nmsa_multiscale_nearest(void* staging_host, void* staging_device, int n_desc, int n_words,
+                            nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,8 @@
 SURVEY.md §8 f4 (the numpy/cv2 preprocessing pipeline itself is out of scope)."""
 from .base import APPLIED_PREPROCESSING_KEY
 from .base import get_applied_preprocessing_meta
+from .multiscale_supervision import MultiscaleSupervisionGenerator
+from .multiscale_supervision import cv2_nearest_map
 from .multiscale_supervision import get_downscale
 from .resize import FULLRES_SUFFIX
 from .resize import get_fullres

@@ -7,13 +7,22 @@ Batch format: `panoptic` i64 [B,H,W]; `panoptic_embedding_keys` i64 [B,K] with
 from typing import Any, Dict
 
 from ... import ops
+from .base import apply_to_downscales
 
 
 class DenseVisualEmbeddingTargetGenerator:
-    def __init__(self, diff_factor: float = 0.65, **kwargs) -> None:
+    def __init__(self, diff_factor: float = 0.65, multiscale_processing: bool = True,
+                 **kwargs) -> None:
         self.diff_factor = diff_factor
+        self._multiscale_processing = multiscale_processing
 
     def __call__(self, batch: Dict[str, Any]) -> Dict[str, Any]:
+        batch = self._preprocess(batch)
+        if self._multiscale_processing:
+            apply_to_downscales(batch, lambda sub, downscale: self._preprocess(sub))
+        return batch
+
+    def _preprocess(self, batch: Dict[str, Any]) -> Dict[str, Any]:
         if 'image_embedding' not in batch or 'panoptic_embedding' not in batch:
             return batch                                      # inference call
         r = ops.dve_targets(batch['panoptic'], batch['panoptic_embedding_keys'],

@@ -11,8 +11,8 @@ leaves it.  Written keys, as a collated reference batch holds them: `orientation
 list of B dicts.  The biternions are computed on the host with the reference's numpy expression,
 so the painted values are bit-identical; the per-image key tables travel in ONE pinned buffer and
 one asynchronous copy, and one small device-to-host copy (flags of the painted keys + status) is
-the only synchronisation.  The `multiscale_processing` plumbing of the numpy pipeline is not
-mirrored: apply the generator to each `_down_<k>` sub-batch.
+the only synchronisation.  With `multiscale_processing` (the reference's default: on) the
+generator runs again on every `batch['_down_<k>']` sub-batch, one such copy per scale.
 """
 from typing import Any, Dict, Optional, Tuple
 
@@ -21,6 +21,7 @@ import torch
 
 from ... import ops
 from ...utils import np_rad2biternion
+from .base import apply_to_downscales
 from .instance import _device_lut
 
 _KEY_PAD = 64               # K is padded to a multiple: the shapes stay stable from batch to batch
@@ -32,8 +33,10 @@ class OrientationTargetGenerator:
         self,
         semantic_classes_estimate_orientation: Optional[Tuple[bool]] = None,     # with void
         max_instances: int = 1024,
+        multiscale_processing: bool = True,
         **kwargs
     ) -> None:
+        self._multiscale_processing = multiscale_processing
         if semantic_classes_estimate_orientation is not None:
             self._estimate = np.asarray(semantic_classes_estimate_orientation, dtype=bool)
             self._n_classes = len(self._estimate)
@@ -75,6 +78,12 @@ class OrientationTargetGenerator:
                 device[B * K:3 * B * K].view(torch.float32).view(B, K, 2))
 
     def __call__(self, batch: Dict[str, Any], n_classes: Optional[int] = None) -> Dict[str, Any]:
+        batch = self._preprocess(batch, n_classes)
+        if self._multiscale_processing:
+            apply_to_downscales(batch, lambda sub, downscale: self._preprocess(sub, n_classes))
+        return batch
+
+    def _preprocess(self, batch: Dict[str, Any], n_classes: Optional[int] = None) -> Dict[str, Any]:
         if not all(k in batch for k in ('instance', 'orientations', 'semantic')):
             return batch                      # inference / no orientation labels (orientation.py:43-47)
         sem, ins, orientations = batch['semantic'], batch['instance'], batch['orientations']

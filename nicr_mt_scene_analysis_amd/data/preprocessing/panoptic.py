@@ -8,12 +8,14 @@ import torch
 
 from ... import ops
 from ...utils.panoptic_merge import _ids_to_dicts
+from .base import apply_to_downscales
 from .instance import _device_lut
 
 
 class PanopticTargetGenerator:
     def __init__(self, semantic_classes_is_thing: Optional[Tuple[bool]] = None,
-                 max_instances: int = 1024, **kwargs) -> None:
+                 max_instances: int = 1024, multiscale_processing: bool = True, **kwargs) -> None:
+        self._multiscale_processing = multiscale_processing
         self._is_thing = None if semantic_classes_is_thing is None else \
             np.asarray(semantic_classes_is_thing, dtype=bool)
         # hypersim has more than 256 instances per image (panoptic.py:36-38)
@@ -24,6 +26,12 @@ class PanopticTargetGenerator:
         self._luts: Dict = {}
 
     def __call__(self, batch: Dict[str, Any], n_classes: Optional[int] = None) -> Dict[str, Any]:
+        batch = self._preprocess(batch, n_classes)
+        if self._multiscale_processing:
+            apply_to_downscales(batch, lambda sub, downscale: self._preprocess(sub, n_classes))
+        return batch
+
+    def _preprocess(self, batch: Dict[str, Any], n_classes: Optional[int] = None) -> Dict[str, Any]:
         if 'instance' not in batch or 'semantic' not in batch:
             return batch
         sem, ins = batch['semantic'], batch['instance']

@@ -5,8 +5,10 @@ synchronisation.  These are thin argument marshallers over include/nmsa.h; the
 reference-shaped classes (model/postprocessing, utils/panoptic_merge, metric,
 loss) are built on top of them.
 """
-from typing import Dict, Optional, Tuple
+import math
+from typing import Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -640,6 +642,141 @@ def dve_project(
         if x is not emb:
             emb.copy_(x)
     return heads[0][2], heads[1][2]
+
+
+# ----------------------------------------------------------------------------- multiscale
+def cv2_nearest_map(src: int, dst: int) -> np.ndarray:
+    """Source index of every destination index of a nearest-neighbour resize of one side from
+    `src` to `dst` elements, as OpenCV's `resizeNN` (cv2.INTER_NEAREST) computes it: in double
+    arithmetic `ifx = 1 / (dst / src)`, `map[x] = min(floor(x * ifx), src - 1)`.  This is NOT
+    `x * src // dst`: src = 116, dst = 14 maps 7 to 57 (x * ifx = 57.99999999999999).  The ONE
+    place the rule lives; the device only reads the resulting int32 maps."""
+    src, dst = int(src), int(dst)
+    if src < 1 or dst < 1:
+        raise ValueError(f'side lengths must be positive, got {src} -> {dst}')
+    ifx = 1.0 / (dst / src)
+    return np.array([min(int(math.floor(x * ifx)), src - 1) for x in range(dst)], dtype=np.int32)
+
+
+_MS_DESC_WORDS = 16         # sizeof(nmsa_multiscale_desc) / 4
+_MS_ALIGN = 256             # every output starts on its own 256 bytes of the one allocation
+# Staging of nmsa_multiscale_nearest, one per (device, stream, shape set): pinned host words
+# (descriptor table | index maps), their device twin, the event of the last copy out of the pinned
+# words, and the layout of the outputs.  The maps and the shape fields are written once; a call
+# only fills in the addresses.  LRU of 8.  A call under hipGraph capture takes the staging of an
+# earlier eager call out of the cache for good: a replay copies the pinned words again, so they
+# are never rewritten and live as long as the process.
+_MS_STAGING: 'collections.OrderedDict[tuple, dict]' = __import__('collections').OrderedDict()
+_MS_CAPTURED = []
+
+
+def _ms_build_staging(sig, downscales, hw, dev) -> dict:
+    h, w = hw
+    shapes = {d: (int(h / d), int(w / d)) for d in downscales}
+    maps, map_at, words = [], {}, 0
+    for d, (hd, wd) in shapes.items():
+        map_at[d] = (words, words + hd)
+        maps += [cv2_nearest_map(h, hd), cv2_nearest_map(w, wd)]
+        words += hd + wd
+    n_desc = len(sig) * len(shapes)
+    host = torch.empty((n_desc * _MS_DESC_WORDS + words,), dtype=torch.int32).pin_memory()
+    packed = host.numpy()
+    packed[:] = 0
+    if maps:
+        packed[n_desc * _MS_DESC_WORDS:] = np.concatenate(maps)
+    table = packed[:n_desc * _MS_DESC_WORDS].reshape(n_desc, _MS_DESC_WORDS)
+    outputs, nbytes, i = [], 0, 0
+    for d, (hd, wd) in shapes.items():
+        for name, shape, dtype in sig:
+            size = torch.empty((), dtype=dtype).element_size()
+            planes = int(np.prod(shape[:-2], dtype=np.int64))
+            table[i, 4:12] = (planes, h, w, hd, wd, size.bit_length() - 1, *map_at[d])
+            outputs.append((d, name, shape[:-2] + (hd, wd), dtype, nbytes, planes * hd * wd * size))
+            nbytes += -(-planes * hd * wd * size // _MS_ALIGN) * _MS_ALIGN
+            i += 1
+    # (the address is taken here, once: the buffer was pinned above, and a pinned-memory query
+    # has no place in a call that may run under hipGraph capture)
+    return {'host': host, 'host_ptr': L.ptr(host), 'addresses': table.view(np.uint64)[:, :2], 'n_desc': n_desc,
+            'device': torch.empty_like(host, device=dev), 'event': None, 'outputs': outputs,
+            'nbytes': nbytes, 'shapes': shapes}
+
+
+def multiscale_nearest(tensors: Dict[str, torch.Tensor], downscales: Sequence[int],
+                       hw: Tuple[int, int]) -> Dict[int, Dict[str, torch.Tensor]]:
+    """reference: MultiscaleSupervisionGenerator._preprocess (multiscale_supervision.py:41-67) ->
+    resize() with cv2.INTER_NEAREST (resize.py:95-161), for a whole batch: every tensor [..., H, W]
+    of `tensors` at every size (int(H / d), int(W / d)), by ONE launch of nmsa_multiscale_nearest
+    behind one asynchronous copy of the descriptor table.  Elements of 1, 2, 4 or 8 bytes move as
+    raw bits.  -> {d: {name: tensor [..., int(H / d), int(W / d)]}}; the outputs of one call are
+    views of one allocation."""
+    h, w = int(hw[0]), int(hw[1])
+    downscales = tuple(downscales)
+    sig, dev = [], None
+    for name, t in tensors.items():
+        _require_on_device(t, name)
+        if dev is not None and t.device != dev:
+            raise ValueError(f'{name} is on {t.device}, the other tensors on {dev}')
+        dev = t.device
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+        if t.ndim < 3 or tuple(t.shape[-2:]) != (h, w):
+            raise ValueError(f'{name} must be [..., {h}, {w}], got shape {tuple(t.shape)}')
+        if t.element_size() not in (1, 2, 4, 8) or t.is_complex():
+            raise ValueError(f'{name}: elements of 1, 2, 4 or 8 bytes are supported, got {t.dtype}')
+        if t.numel() == 0:
+            raise ValueError(f'{name} is empty: shape {tuple(t.shape)}')
+        sig.append((name, tuple(int(n) for n in t.shape), t.dtype))
+    for d in downscales:
+        if d <= 0 or int(h / d) == 0 or int(w / d) == 0:
+            raise ValueError(f'downscale {d} of {h} x {w} is empty')
+    if not sig or not downscales:
+        return {d: {} for d in downscales}
+    if len(sig) * len(set(downscales)) > 1024:                    # NMSA_MULTISCALE_MAX_DESC
+        raise ValueError('more than 1024 (key, scale) pairs in one call')
+    capturing = torch.cuda.is_current_stream_capturing()
+    shape_set = (dev, h, w, downscales, tuple(sig))
+    if capturing:
+        # pinned memory cannot be allocated while a stream captures: the capture takes over the
+        # staging of an earlier eager call with these shapes (the warm-up run every capture needs
+        # anyway; its copy has run: torch.cuda.graph synchronises the device on entry), and
+        # later eager calls build their own
+        key = next((k for k in _MS_STAGING if k[:-1] == shape_set), None)
+        if key is None:
+            raise RuntimeError('multiscale_nearest under hipGraph capture: call it once with these '
+                               'shapes before the capture (its pinned staging cannot be allocated '
+                               'while a stream captures)')
+        st = _MS_STAGING.pop(key)
+        _MS_CAPTURED.append(st)
+    else:
+        key = shape_set + (torch.cuda.current_stream(dev).cuda_stream,)
+        st = _MS_STAGING.get(key)
+        if st is None:
+            st = _MS_STAGING[key] = _ms_build_staging(sig, downscales, (h, w), dev)
+            while len(_MS_STAGING) > 8:
+                _, dropped = _MS_STAGING.popitem(last=False)
+                if dropped['event'] is not None:
+                    dropped['event'].synchronize()      # its last copy still reads the pinned words
+        else:
+            _MS_STAGING.move_to_end(key)
+            # the copy of the call before reads the pinned words: it must have run (a wait on that
+            # one copy, not on the stream: it returns at once unless the device is a whole call behind)
+            if st['event'] is not None:
+                st['event'].synchronize()
+    out = torch.empty((st['nbytes'],), dtype=torch.uint8, device=dev)
+    base = out.data_ptr()
+    for i, (d, name, shape, dtype, at, nbytes) in enumerate(st['outputs']):
+        st['addresses'][i] = (tensors[name].data_ptr(), base + at)
+    L.check(L.lib().nmsa_multiscale_nearest(
+        st['host_ptr'], L.ptr(st['device']), st['n_desc'], int(st['host'].numel()),
+        L.stream_ptr(dev)), 'nmsa_multiscale_nearest')
+    if not capturing:
+        if st['event'] is None:
+            st['event'] = torch.cuda.Event()
+        st['event'].record(torch.cuda.current_stream(dev))
+    result: Dict[int, Dict[str, torch.Tensor]] = {d: {} for d in st['shapes']}
+    for d, name, shape, dtype, at, nbytes in st['outputs']:
+        result[d][name] = out[at:at + nbytes].view(dtype).view(shape)
+    return result
 
 
 # ----------------------------------------------------------------------------- normals

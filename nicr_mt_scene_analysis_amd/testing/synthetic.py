@@ -15,6 +15,7 @@ Layouts/dtypes follow what the reference's decoders/targets produce:
   orientation      [B,2,H,W] f32 unit biternion (cos, sin)
 """
 import hashlib
+import json
 from typing import Dict
 
 import numpy as np
@@ -586,3 +587,55 @@ def make_orientation_inputs(recipe: str, seed: int) -> Dict:
         orientations.append(d)
     return {'semantic': sem, 'instance': ins, 'estimate': np.arange(C) % 2 == 1,
             'orientations': orientations}
+
+
+# ---- side-output targets (data/preprocessing/multiscale_supervision.py) -------------------------
+# recipe -> (B, n_classes, H, W, random instances per image, downscales, sigma, sigma per downscale)
+MULTISCALE_RECIPES = {
+    'A': (2, 9, 58, 116, 16, (4, 8), 4, {4: 2, 8: 1}),         # 116 -> 14 and 58 -> 14: floor(x / scale) is not x * src // dst
+    'B': (3, 9, 50, 70, 14, (8, 16, 32), 4, {8: 2, 16: 1, 32: 1}),      # the last scale is 1 x 2
+    'C': (1, 9, 48, 64, 12, (2, 4), 4, {2: 3, 4: 2}),          # divisible: equals [::d, ::d]
+}
+MULTISCALE_SPATIAL_KEYS = ('semantic', 'instance', 'depth', 'normal', 'valid', 'segment_ids')
+MULTISCALE_KEYS = MULTISCALE_SPATIAL_KEYS + ('orientations', 'scene')
+
+
+def make_multiscale_inputs(recipe: str, seed: int) -> Dict:
+    """A collated batch for the side-output target chain, one entry per element size and layout:
+    `semantic` u8 and `instance` i32 [B,H,W] of `make_label_maps`, `depth` i16 [B,H,W] over the
+    whole int16 range, `normal` f32 [B,3,H,W] with NaNs of several payloads, -0.0, +-inf and
+    denormals strewn in, `valid` bool [B,H,W], `segment_ids` u32 [B,H,W] above 2^16 (the
+    reference's uint32 path; the device batch holds it as i64), `orientations` one dict {instance
+    id: angle} per image and `scene` i64 [B] (not spatial: copied).  Odd classes are the ones
+    whose orientation is estimated."""
+    B, C, H, W, n_inst, _, _, _ = MULTISCALE_RECIPES[recipe]
+    maps = make_label_maps(B, C, H, W, n_instances=n_inst, seed=seed)
+    sem, ins = maps['semantic'], maps['instance']
+    rng = np.random.default_rng(seed + 104729)
+    depth = rng.integers(-32768, 32768, (B, H, W)).astype(np.int16)
+    normal = rng.standard_normal((B, 3, H, W)).astype(np.float32)
+    bits = normal.view(np.uint32)
+    special = np.array([0x7fc00000, 0xffc00001, 0x7f800123, 0x80000000, 0x00000000, 0x7f800000,
+                        0xff800000, 0x00000001, 0x807fffff], np.uint32)
+    strewn = rng.random(normal.shape) < 0.2
+    bits[strewn] = rng.choice(special, size=int(strewn.sum()))
+    valid = rng.random((B, H, W)) < 0.5
+    segment_ids = (sem.astype(np.uint32) << 16) + ins.astype(np.uint32) + np.uint32(0x80000000) * \
+        (rng.random((B, H, W)) < 0.25)
+    orientations = []
+    for b in range(B):
+        orientations.append({int(i): float(rng.uniform(-np.pi, 3.0 * np.pi))
+                             for i in np.unique(ins[b]) if i != 0 and rng.random() < 0.8})
+    return {'semantic': sem, 'instance': ins, 'depth': depth, 'normal': normal, 'valid': valid,
+            'segment_ids': segment_ids, 'orientations': orientations,
+            'scene': rng.integers(0, 5, (B,)).astype(np.int64),
+            'semantic_classes_is_thing': maps['semantic_classes_is_thing'],
+            'estimate': np.arange(C) % 2 == 1}
+
+
+def multiscale_input_digest(inp: Dict) -> str:
+    """SHA-256 over everything `make_multiscale_inputs` returns (fixture and tests compare it)"""
+    angles = json.dumps([[[int(k), float(v)] for k, v in d.items()] for d in inp['orientations']])
+    return input_digest(*(inp[k] for k in MULTISCALE_SPATIAL_KEYS), inp['scene'],
+                        inp['semantic_classes_is_thing'], inp['estimate'],
+                        np.frombuffer(angles.encode(), dtype=np.uint8))
