@@ -779,9 +779,21 @@ int nmsa_multitask_loss_bwd_unless(const nmsa_loss_item* items_host, int n_items
  * inf or 0 as its factor here.  Supported magnitudes are those whose sum of squares is a normal
  * float32.  NMSA_ERR_ARG: NULL / non-positive arguments, H*W above 2^31 - 1, more than 2^31 - 1
  * workgroups.  No workspace.
+ *
+ * nmsa_dve_project_route: which kernel nmsa_dve_project runs for the same arguments (the launch
+ * switches on this function's answer and on nothing else; the pointers are only looked at for
+ * NULL and alignment, nothing is launched).  NMSA_DVE_KERNEL_GENERIC (0) for the per-pixel kernel,
+ * PT * 16 + NT for the MFMA instantiation with 16 PT pixels per wave and NT tiles of 16 classes
+ * per pass (131 = <8,3>, 67 = <4,3>, 70 = <4,6>), or the negative NMSA_ERR_* nmsa_dve_project
+ * would return.  Up to three class tiles over both heads: <8,3> when B * ceil(H*W / 128) is at
+ * least 8 waves per compute unit (nmsa_device_geometry), else <4,3>; more tiles: <4,6>.
  * ------------------------------------------------------------------------- */
 #define NMSA_DVE_ROUTE_AUTO 0
 #define NMSA_DVE_ROUTE_GENERIC 1
+#define NMSA_DVE_KERNEL_GENERIC 0
+int nmsa_dve_project_route(const float* emb, int B, int D, int H, int W,
+                           const float* weight_a, int Ca, const float* logits_a,
+                           const float* weight_b, int Cb, const float* logits_b, int route);
 int nmsa_dve_project(float* emb, int B, int D, int H, int W,
                      const float* weight_a, int Ca, float* logits_a,
                      const float* weight_b, int Cb, float* logits_b,

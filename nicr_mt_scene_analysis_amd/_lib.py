@@ -86,6 +86,7 @@ _SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     'nmsa_dve_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'nmsa_dve_project': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    'nmsa_dve_project_route': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     'nmsa_normal_valid_mask': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'nmsa_rmse_update': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                               _vp, _vp, _vp]),

@@ -22,6 +22,7 @@
 // lane per pixel, plain fmaf.  Both routes compute dot(x, w) * (1 / sqrt(sum x^2)) and
 // x * (1 / sqrt(sum x^2)): a zero vector gives NaN everywhere (0 * inf), inf / NaN propagate.
 // (The factor form needs the sum of squares to be a normal float32: see include/nmsa.h.)
+// Which kernel runs is decided by dve_route alone; nmsa_dve_project_route exports its answer.
 #include "nmsa_common.hpp"
 
 namespace nmsa {
@@ -228,8 +229,7 @@ template <int PT, int NT>
 int launch_tuned(float* emb, const DveHeads& h, int B, int D, int HW, hipStream_t stream)
 {
     const int tiles_per_img = (HW + 16 * PT - 1) / (16 * PT);
-    const long long n_tiles = (long long)B * tiles_per_img;
-    if (n_tiles > 0x7fffffffLL - 4) return NMSA_ERR_ARG;
+    const long long n_tiles = (long long)B * tiles_per_img;                 // dve_route: fits an int
     const unsigned blocks = (unsigned)((n_tiles + 3) / 4);
     hipLaunchKernelGGL((k_dve_project<PT, NT>), dim3(blocks), dim3(256), 0, stream, emb, h, D, HW,
                        tiles_per_img, (int)n_tiles);
@@ -238,27 +238,24 @@ int launch_tuned(float* emb, const DveHeads& h, int B, int D, int HW, hipStream_
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-}  // namespace
-}  // namespace nmsa
+constexpr int tuned_route(int PT, int NT) { return PT * 16 + NT; }
 
-using namespace nmsa;
-
-extern "C" int nmsa_dve_project(float* emb, int B, int D, int H, int W,
-                                const float* weight_a, int Ca, float* logits_a,
-                                const float* weight_b, int Cb, float* logits_b,
-                                int route, nmsa_stream_t stream_)
+// THE route rule: validates the arguments, fills `h` and answers NMSA_DVE_KERNEL_GENERIC (0),
+// PT * 16 + NT of the k_dve_project instantiation, or the NMSA_ERR_* the call returns.  Launches
+// nothing; nmsa_dve_project switches on the answer and on nothing else.
+int dve_route(const float* emb, int B, int D, int H, int W,
+              const float* weight_a, int Ca, const float* logits_a,
+              const float* weight_b, int Cb, const float* logits_b, int route, DveHeads& h)
 {
     if (!emb || B < 1 || D < 1 || H < 1 || W < 1) return NMSA_ERR_ARG;
     if (weight_a && (Ca < 1 || !logits_a)) return NMSA_ERR_ARG;
     if (weight_b && (Cb < 1 || !logits_b)) return NMSA_ERR_ARG;
     if (route != NMSA_DVE_ROUTE_AUTO && route != NMSA_DVE_ROUTE_GENERIC) return NMSA_ERR_ARG;
     if ((long long)H * W > 0x7fffffffLL) return NMSA_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
     const int HW = H * W;
 
-    DveHeads h;
-    h.w[0] = weight_a; h.out[0] = logits_a; h.C[0] = weight_a ? Ca : 0;
-    h.w[1] = weight_b; h.out[1] = logits_b; h.C[1] = weight_b ? Cb : 0;
+    h.w[0] = weight_a; h.out[0] = const_cast<float*>(logits_a); h.C[0] = weight_a ? Ca : 0;
+    h.w[1] = weight_b; h.out[1] = const_cast<float*>(logits_b); h.C[1] = weight_b ? Cb : 0;
     h.tiles[0] = (h.C[0] + 15) / 16;
     h.tiles[1] = (h.C[1] + 15) / 16;
     const int T = h.tiles[0] + h.tiles[1];
@@ -268,19 +265,54 @@ extern "C" int nmsa_dve_project(float* emb, int B, int D, int H, int W,
         (!weight_a || (aligned16(weight_a) && aligned16(logits_a))) &&
         (!weight_b || (aligned16(weight_b) && aligned16(logits_b)));
     if (!tuned) {
-        const size_t total = (size_t)B * (size_t)HW;
-        const size_t blocks = (total + 255) / 256;
-        if (blocks > 0x7fffffffull) return NMSA_ERR_ARG;
-        hipLaunchKernelGGL(k_dve_generic, dim3((unsigned)blocks), dim3(256), 0, stream, emb, h, D, HW, total);
-        return check_launch();
+        const size_t blocks = ((size_t)B * (size_t)HW + 255) / 256;
+        return blocks > 0x7fffffffull ? NMSA_ERR_ARG : NMSA_DVE_KERNEL_GENERIC;
     }
     // up to 48 classes in one pass: 128 pixels per wave while that still gives every SIMD of the
     // device two waves, 64 pixels on small maps; more classes: 64 pixels x 96 classes per pass
+    int PT = 4;
     if (T <= 3) {
         const DeviceGeometry g = device_geometry();
         const long long waves128 = (long long)B * ((HW + 127) / 128);
-        if (waves128 >= (long long)g.cus * 4 * 2) return launch_tuned<8, 3>(emb, h, B, D, HW, stream);
-        return launch_tuned<4, 3>(emb, h, B, D, HW, stream);
+        if (waves128 >= (long long)g.cus * 4 * 2) PT = 8;
     }
-    return launch_tuned<4, 6>(emb, h, B, D, HW, stream);
+    const long long n_tiles = (long long)B * ((HW + 16 * PT - 1) / (16 * PT));
+    if (n_tiles > 0x7fffffffLL - 4) return NMSA_ERR_ARG;
+    return tuned_route(PT, T <= 3 ? 3 : 6);
+}
+
+}  // namespace
+}  // namespace nmsa
+
+using namespace nmsa;
+
+extern "C" int nmsa_dve_project_route(const float* emb, int B, int D, int H, int W,
+                                      const float* weight_a, int Ca, const float* logits_a,
+                                      const float* weight_b, int Cb, const float* logits_b, int route)
+{
+    DveHeads h;
+    return dve_route(emb, B, D, H, W, weight_a, Ca, logits_a, weight_b, Cb, logits_b, route, h);
+}
+
+extern "C" int nmsa_dve_project(float* emb, int B, int D, int H, int W,
+                                const float* weight_a, int Ca, float* logits_a,
+                                const float* weight_b, int Cb, float* logits_b,
+                                int route, nmsa_stream_t stream_)
+{
+    DveHeads h;
+    const int kernel = dve_route(emb, B, D, H, W, weight_a, Ca, logits_a, weight_b, Cb, logits_b, route, h);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int HW = H * W;
+    switch (kernel) {
+    case NMSA_DVE_KERNEL_GENERIC: {
+        const size_t total = (size_t)B * (size_t)HW;
+        hipLaunchKernelGGL(k_dve_generic, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                           emb, h, D, HW, total);
+        return check_launch();
+    }
+    case tuned_route(8, 3): return launch_tuned<8, 3>(emb, h, B, D, HW, stream);
+    case tuned_route(4, 3): return launch_tuned<4, 3>(emb, h, B, D, HW, stream);
+    case tuned_route(4, 6): return launch_tuned<4, 6>(emb, h, B, D, HW, stream);
+    default: return kernel < 0 ? kernel : NMSA_ERR_ARG;    // an error of the rule
+    }
 }

@@ -595,18 +595,9 @@ def dve_targets(
     return {'indices': idx, 'lut': lut}
 
 
-def dve_project(
-    emb: torch.Tensor,
-    weight_a: Optional[torch.Tensor] = None,
-    weight_b: Optional[torch.Tensor] = None,
-    *,
-    generic: bool = False,
-) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """reference: DenseVisualEmbeddingPostprocessing (dense_visual_embedding.py:126 + :81) —
-    `emb /= emb.norm(dim=1, keepdim=True)` IN PLACE, then `F.conv2d(emb, weight[:, :, None, None])`
-    for up to two [C, D] class-embedding matrices, all from one pass over `emb`.  Returns
-    (logits_a, logits_b); None for a head that is off.  `generic` selects the plain per-pixel
-    kernel on shapes the MFMA kernel would take (tests)."""
+def _dve_project_args(emb, weight_a, weight_b):
+    """checked arguments of `nmsa_dve_project`: (B, D, H, W), the contiguous map and per head
+    (weight, C, freshly allocated logits) or (None, 0, None)"""
     if emb.dtype != torch.float32:
         raise TypeError(f'emb must be float32, got {emb.dtype}')
     if not emb.is_cuda:
@@ -634,14 +625,50 @@ def dve_project(
         heads.append((w, Cn, torch.empty((B, Cn, H, W), dtype=torch.float32, device=dev)))
     # cold path: a strided map is normalised through a contiguous copy and copied back
     x = emb if emb.is_contiguous() else emb.contiguous()
+    return (B, D, H, W), x, heads
+
+
+def dve_project(
+    emb: torch.Tensor,
+    weight_a: Optional[torch.Tensor] = None,
+    weight_b: Optional[torch.Tensor] = None,
+    *,
+    generic: bool = False,
+) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """reference: DenseVisualEmbeddingPostprocessing (dense_visual_embedding.py:126 + :81) —
+    `emb /= emb.norm(dim=1, keepdim=True)` IN PLACE, then `F.conv2d(emb, weight[:, :, None, None])`
+    for up to two [C, D] class-embedding matrices, all from one pass over `emb`.  Returns
+    (logits_a, logits_b); None for a head that is off.  `generic` selects the plain per-pixel
+    kernel on shapes the MFMA kernel would take (tests)."""
+    (B, D, H, W), x, heads = _dve_project_args(emb, weight_a, weight_b)
     if x.numel():
         (wa, Ca, la), (wb, Cb, lb) = heads
         L.check(L.lib().nmsa_dve_project(
             L.ptr(x), B, D, H, W, L.ptr(wa), Ca, L.ptr(la), L.ptr(wb), Cb, L.ptr(lb),
-            1 if generic else 0, L.stream_ptr(dev)), 'nmsa_dve_project')
+            1 if generic else 0, L.stream_ptr(emb.device)), 'nmsa_dve_project')
         if x is not emb:
             emb.copy_(x)
     return heads[0][2], heads[1][2]
+
+
+def dve_project_route(
+    emb: torch.Tensor,
+    weight_a: Optional[torch.Tensor] = None,
+    weight_b: Optional[torch.Tensor] = None,
+    *,
+    generic: bool = False,
+) -> int:
+    """The kernel `dve_project` runs for these arguments (`nmsa_dve_project_route`): 0 for the
+    per-pixel kernel, PT * 16 + NT for the MFMA instantiation `<PT, NT>` (131, 67, 70).  The logits
+    are allocated as `dve_project` allocates them, so the alignment seen here is the launch's;
+    nothing is launched and `emb` is left alone."""
+    (B, D, H, W), x, heads = _dve_project_args(emb, weight_a, weight_b)
+    (wa, Ca, la), (wb, Cb, lb) = heads
+    rc = L.lib().nmsa_dve_project_route(
+        L.ptr(x), B, D, H, W, L.ptr(wa), Ca, L.ptr(la), L.ptr(wb), Cb, L.ptr(lb), 1 if generic else 0)
+    if rc < 0:
+        L.check(rc, 'nmsa_dve_project_route')
+    return rc
 
 
 # ----------------------------------------------------------------------------- multiscale
