@@ -929,6 +929,70 @@ typedef struct nmsa_multiscale_desc {
 int nmsa_multiscale_nearest(void* staging_host, void* staging_device, int n_desc, int n_words,
                             nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * batch augmentation (csrc/augment.hip)
+ *
+ * nmsa_batch_augment: RandomCrop (data/preprocessing/crop.py:57-73, the slices), then
+ *   RandomHorizontalFlip (flip.py:40-47, np.flip(axis=1) of the crop), NormalizeRGB /
+ *   NormalizeDepth (normalize.py:13-31, 109-122) and ToTorchTensors' HWC -> CHW (torch.py:31-38),
+ *   for every key of a collated batch in ONE launch: per descriptor, sample b, channel c and
+ *   output pixel (y, x),
+ *     dst[b, c, y, x] = f(src[b, y0[b] + y, flip[b] ? x0[b] + w - 1 - x : x0[b] + x, c]).
+ *   staging_host   PINNED host memory, n_words 32-bit words, 8-byte aligned: n_desc descriptors
+ *                  (24 words each) followed by the per-sample parameters, n_samples triples of
+ *                  int32 (y0, x0, flip), shared by all descriptors.
+ *   staging_device device memory of the same size; the call enqueues ONE asynchronous copy of the
+ *                  staging buffer and the launch.  `block_begin` and `pixels_per_lane` of every
+ *                  descriptor are written by the call (into staging_host) before the copy.
+ *   mode NMSA_AUGMENT_MOVE        elements move as raw bits of 1 << log2_size bytes (1, 2, 4, 8),
+ *                                 [B,H,W,C] -> [B,C,h,w] ([B,H,W] is C == 1): no conversion of
+ *                                 any kind, NaN payloads and -0.0 survive.
+ *        NMSA_AUGMENT_RGB_NORM    uint8 [B,H,W,3] -> float32 [B,3,h,w], (float(v) - mean[c]) /
+ *                                 std[c]: one IEEE subtract, then one IEEE divide.  mean / std are
+ *                                 the caller's float32 values (numpy's float32(0.485) * 255, ...).
+ *        NMSA_AUGMENT_DEPTH_NORM  uint16 (log2_size 1) or float32 (log2_size 2) [B,H,W] -> float32
+ *                                 [B,1,h,w], (float(v) - mean[0]) / std[0]; with raw_depth, a
+ *                                 source element with float(v) == invalid_depth_value is written
+ *                                 as invalid_depth_value itself (-0.0 against 0.0 gives +0.0).
+ *   Every field and every sample's window are checked on the host copy before anything is
+ *   enqueued: NMSA_ERR_ARG for NULL or misaligned pointers (source: its element size,
+ *   destination: its element size), non-positive fields, B != n_samples, h > H or w > W, a
+ *   negative y0 / x0, y0 + h > H or x0 + w > W, a flip outside {0, 1}, an unknown mode, a
+ *   log2_size the mode does not take, C != 3 for RGB_NORM or C != 1 for DEPTH_NORM, a std of 0,
+ *   an out_dtype other than NMSA_F32 / NMSA_F16, B * C * h * w above 2^31 - 1, n_desc above
+ *   NMSA_AUGMENT_MAX_DESC, n_words below the table and the parameters.  NMSA_ERR_UNSUPPORTED for
+ *   out_dtype NMSA_F16 (the reference's `output_dtype='float16'`).  out_dtype is read for the
+ *   two normalising modes only.  No workspace, no host synchronisation; capturable in a hipGraph
+ *   (a replay copies the pinned buffer again: a captured call needs a staging buffer that no
+ *   later call rewrites; parameters written into it between replays are NOT checked again, the
+ *   writer keeps them inside the windows above).
+ * ------------------------------------------------------------------------- */
+#define NMSA_AUGMENT_MAX_DESC 256
+#define NMSA_AUGMENT_MOVE 0
+#define NMSA_AUGMENT_RGB_NORM 1
+#define NMSA_AUGMENT_DEPTH_NORM 2
+typedef struct nmsa_augment_desc {
+    uint64_t src;               /* device address of the source, [B, H, W, C]                  */
+    uint64_t dst;               /* device address of the destination, [B, C, h, w]             */
+    int32_t B;                  /* samples: equals n_samples                                   */
+    int32_t H, W;               /* source side lengths                                         */
+    int32_t C;                  /* interleaved channels of the source, planes of the result    */
+    int32_t h, w;               /* crop side lengths                                           */
+    int32_t mode;               /* NMSA_AUGMENT_*                                              */
+    int32_t log2_size;          /* log2 of the SOURCE element size in bytes                    */
+    int32_t out_dtype;          /* NMSA_F32 (the normalising modes)                            */
+    int32_t raw_depth;          /* DEPTH_NORM: keep invalid_depth_value                        */
+    int32_t block_begin;        /* first workgroup of this descriptor: written by the call     */
+    int32_t pixels_per_lane;    /* 4 where w % 4 == 0 and dst allows vector stores, else 1:
+                                   written by the call                                         */
+    float mean[3];              /* RGB_NORM: per channel; DEPTH_NORM: [0]                      */
+    float std[3];
+    float invalid_depth_value;
+    int32_t reserved;
+} nmsa_augment_desc;
+int nmsa_batch_augment(void* staging_host, void* staging_device, int n_desc, int n_samples,
+                       int n_words, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,7 @@ _SIGNATURES = {
                                       _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp,
                                       _i, _vp, _vp, _vp, _vp]),
     'nmsa_multiscale_nearest': (_i, [_vp, _vp, _i, _i, _vp]),
+    'nmsa_batch_augment': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

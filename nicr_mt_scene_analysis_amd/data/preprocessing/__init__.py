@@ -1,5 +1,8 @@
 """The batch helpers the hot-path callers use, plus the on-device target generators of
-SURVEY.md §8 f4 (the numpy/cv2 preprocessing pipeline itself is out of scope)."""
+SURVEY.md §8 f4 and `BatchAugmentation`, the numpy steps of the reference's training chain (crop, flip, normalise,
+HWC -> CHW) in one launch; the chain's cv2 steps (`RandomResize`, `RandomHSVJitter`, the upscale of
+`RandomCrop`) stay out of scope."""
+from .augmentation import BatchAugmentation
 from .base import APPLIED_PREPROCESSING_KEY
 from .base import get_applied_preprocessing_meta
 from .multiscale_supervision import MultiscaleSupervisionGenerator

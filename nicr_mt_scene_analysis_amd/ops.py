@@ -806,6 +806,175 @@ def multiscale_nearest(tensors: Dict[str, torch.Tensor], downscales: Sequence[in
     return result
 
 
+# ----------------------------------------------------------------------------- batch augmentation
+_AUG_DESC_WORDS = 24        # sizeof(nmsa_augment_desc) / 4
+_AUG_MODES = {'move': 0, 'rgb_norm': 1, 'depth_norm': 2}
+# Staging of nmsa_batch_augment, one per (device, stream, shape set), kept and handed to captures
+# exactly as _MS_STAGING above: LRU of 8, a call under hipGraph capture takes the staging of an
+# earlier eager call out of the cache for good.
+_AUG_STAGING: 'collections.OrderedDict[tuple, AugmentStaging]' = __import__('collections').OrderedDict()
+_AUG_CAPTURED = []
+
+
+def check_augment_params(params, B: int, source_hw: Tuple[int, int], crop_hw: Tuple[int, int]) -> np.ndarray:
+    """`params` as the int32 [B,3] table of (y0, x0, flip) per sample, every window inside the
+    source and every flip 0 or 1 (the checks of nmsa_batch_augment, with a message)"""
+    table = np.asarray(params)
+    if table.shape != (B, 3) or table.dtype.kind not in 'iub':
+        raise ValueError(f'params must be {B} integer triples (y0, x0, flip), got {table.dtype} {table.shape}')
+    table = table.astype(np.int64)
+    (H, W), (h, w) = source_hw, crop_hw
+    if (table[:, :2] < 0).any() or (table[:, 0] + h > H).any() or (table[:, 1] + w > W).any():
+        raise ValueError(f'a crop window of {h} x {w} leaves the {H} x {W} source: {table[:, :2].tolist()}')
+    if not np.isin(table[:, 2], (0, 1)).all():
+        raise ValueError(f'flip must be 0 or 1, got {table[:, 2].tolist()}')
+    return table.astype(np.int32)
+
+
+class AugmentStaging:
+    """Staging of one shape set of `batch_augment`: pinned host words (descriptor table | (y0, x0,
+    flip) per sample), their device twin, the event of the last copy out of the pinned words and
+    the layout of the outputs.  Shapes, modes and constants are written once; a call fills in the
+    addresses and the parameters.  A hipGraph that captured a call re-reads the pinned words at
+    every replay: `write_params` puts a new table there for the next replay."""
+
+    def __init__(self, sig, B, source_hw, crop_hw, dev) -> None:
+        (H, W), (h, w) = source_hw, crop_hw
+        self.B, self.source_hw, self.crop_hw, self.n_desc = B, source_hw, crop_hw, len(sig)
+        self.host = torch.empty((self.n_desc * _AUG_DESC_WORDS + 3 * B,), dtype=torch.int32).pin_memory()
+        packed = self.host.numpy()
+        packed[:] = 0
+        table = packed[:self.n_desc * _AUG_DESC_WORDS].reshape(self.n_desc, _AUG_DESC_WORDS)
+        self.params = packed[self.n_desc * _AUG_DESC_WORDS:].reshape(B, 3)
+        self.outputs, self.nbytes = [], 0
+        for i, (name, shape, dtype, mode, consts) in enumerate(sig):
+            C = shape[3] if len(shape) == 4 else 1
+            size = torch.empty((), dtype=dtype).element_size()
+            table[i, 4:12] = (B, H, W, C, h, w, _AUG_MODES[mode], size.bit_length() - 1)
+            out_dtype = dtype
+            if mode != 'move':
+                mean, std, raw_depth, invalid = consts
+                out_dtype = torch.float32
+                table[i, 12:14] = (L.NMSA_F32, int(raw_depth))
+                table[i, 16:16 + C].view(np.float32)[:] = mean
+                table[i, 19:19 + C].view(np.float32)[:] = std
+                table[i, 22:23].view(np.float32)[:] = invalid
+            out_shape = (B, h, w) if len(shape) == 3 and mode == 'move' else (B, C, h, w)
+            nbytes = B * C * h * w * torch.empty((), dtype=out_dtype).element_size()
+            self.outputs.append((name, out_shape, out_dtype, self.nbytes, nbytes))
+            self.nbytes += -(-nbytes // _MS_ALIGN) * _MS_ALIGN
+        # (the address is taken here, once: see _ms_build_staging)
+        self.host_ptr = L.ptr(self.host)
+        self.addresses = table.view(np.uint64)[:, :2]
+        self.device = torch.empty_like(self.host, device=dev)
+        self.event = None
+
+    def write_params(self, params) -> None:
+        """(y0, x0, flip) per sample for the next replay of the graph that captured this staging;
+        checked here, because a replay does not pass through the entry point's checks again"""
+        self.params[:] = check_augment_params(params, self.B, self.source_hw, self.crop_hw)
+
+
+def batch_augment(tensors: Dict[str, torch.Tensor], params, crop_hw: Tuple[int, int],
+                  norm: Optional[Dict[str, tuple]] = None, return_staging: bool = False):
+    """reference: RandomCrop (crop.py:57-73) -> RandomHorizontalFlip (flip.py:40-47) ->
+    NormalizeRGB / NormalizeDepth (normalize.py) -> ToTorchTensors (torch.py:31-38), for a whole
+    collated batch by ONE launch of nmsa_batch_augment behind one asynchronous copy of the
+    descriptor table.  `tensors`: contiguous [B,H,W] or channels-last [B,H,W,C] device tensors of
+    one B, H, W.  `params`: integer [B,3], (y0, x0, flip) per sample.  `norm[name]` is
+    ('rgb_norm', mean[3], std[3]) for a uint8 [B,H,W,3] entry or ('depth_norm', mean, std,
+    raw_depth, invalid_depth_value) for a uint16 / float32 [B,H,W] entry; the constants are used as
+    float32.  Every other entry moves as raw bits of 1, 2, 4 or 8 bytes.  -> {name: [B,h,w] for
+    [B,H,W], [B,C,h,w] for [B,H,W,C], float32 [B,3,h,w] / [B,1,h,w] for the normalised entries};
+    the outputs of one call are views of one allocation.  With `return_staging` the
+    `AugmentStaging` used comes back as well (under capture: the one the graph keeps reading)."""
+    h, w = int(crop_hw[0]), int(crop_hw[1])
+    norm = norm or {}
+    sig, dev, BHW = [], None, None
+    for name, t in tensors.items():
+        _require_on_device(t, name)
+        if dev is not None and t.device != dev:
+            raise ValueError(f'{name} is on {t.device}, the other tensors on {dev}')
+        dev = t.device
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+        if t.ndim not in (3, 4) or t.numel() == 0:
+            raise ValueError(f'{name} must be a non-empty [B,H,W] or [B,H,W,C], got shape {tuple(t.shape)}')
+        if BHW is not None and tuple(t.shape[:3]) != BHW:
+            raise ValueError(f'{name} is {tuple(t.shape[:3])}, the other tensors {BHW}')
+        BHW = tuple(int(n) for n in t.shape[:3])
+        spec = norm.get(name, ('move',))
+        if spec[0] == 'move':
+            if t.element_size() not in (1, 2, 4, 8) or t.is_complex():
+                raise ValueError(f'{name}: elements of 1, 2, 4 or 8 bytes are supported, got {t.dtype}')
+            consts = None
+        elif spec[0] == 'rgb_norm':
+            if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[3] != 3:
+                raise ValueError(f'{name}: rgb_norm takes uint8 [B,H,W,3], got {t.dtype} {tuple(t.shape)}')
+            mean, std = (tuple(float(np.float32(v)) for v in vs) for vs in spec[1:3])
+            if len(mean) != 3 or len(std) != 3:
+                raise ValueError(f'{name}: rgb_norm takes three means and three stds')
+            consts = (mean, std, False, 0.0)
+        elif spec[0] == 'depth_norm':
+            if t.dtype not in (torch.uint16, torch.float32) or t.ndim != 3:
+                raise ValueError(f'{name}: depth_norm takes uint16 or float32 [B,H,W], got {t.dtype} {tuple(t.shape)}')
+            consts = ((float(np.float32(spec[1])),), (float(np.float32(spec[2])),), bool(spec[3]),
+                      float(np.float32(spec[4])))
+        else:
+            raise ValueError(f'{name}: unknown mode {spec[0]!r}')
+        if consts is not None and 0.0 in consts[1]:
+            raise ValueError(f'{name}: a std of 0')
+        sig.append((name, tuple(int(n) for n in t.shape), t.dtype, spec[0], consts))
+    if set(norm) - set(tensors):
+        raise KeyError(f'norm names entries that are not in tensors: {sorted(set(norm) - set(tensors))}')
+    if not sig:
+        return ({}, None) if return_staging else {}
+    if len(sig) > 256:                                            # NMSA_AUGMENT_MAX_DESC
+        raise ValueError('more than 256 keys in one call')
+    B, H, W = BHW
+    if h <= 0 or w <= 0 or h > H or w > W:
+        raise ValueError(f'a crop of {h} x {w} does not fit the {H} x {W} source')
+    table = check_augment_params(params, B, (H, W), (h, w))
+    capturing = torch.cuda.is_current_stream_capturing()
+    shape_set = (dev, h, w, tuple(sig))
+    if capturing:
+        # (why: see multiscale_nearest)
+        key = next((k for k in _AUG_STAGING if k[:-1] == shape_set), None)
+        if key is None:
+            raise RuntimeError('batch_augment under hipGraph capture: call it once with these shapes '
+                               'before the capture (its pinned staging cannot be allocated while a '
+                               'stream captures)')
+        st = _AUG_STAGING.pop(key)
+        _AUG_CAPTURED.append(st)
+    else:
+        key = shape_set + (torch.cuda.current_stream(dev).cuda_stream,)
+        st = _AUG_STAGING.get(key)
+        if st is None:
+            st = _AUG_STAGING[key] = AugmentStaging(sig, B, (H, W), (h, w), dev)
+            while len(_AUG_STAGING) > 8:
+                _, dropped = _AUG_STAGING.popitem(last=False)
+                if dropped.event is not None:
+                    dropped.event.synchronize()         # its last copy still reads the pinned words
+        else:
+            _AUG_STAGING.move_to_end(key)
+            if st.event is not None:
+                st.event.synchronize()                  # the copy of the call before has run
+    out = torch.empty((st.nbytes,), dtype=torch.uint8, device=dev)
+    base = out.data_ptr()
+    for i, (name, shape, dtype, at, nbytes) in enumerate(st.outputs):
+        st.addresses[i] = (tensors[name].data_ptr(), base + at)
+    st.params[:] = table
+    L.check(L.lib().nmsa_batch_augment(
+        st.host_ptr, L.ptr(st.device), st.n_desc, B, int(st.host.numel()), L.stream_ptr(dev)),
+        'nmsa_batch_augment')
+    if not capturing:
+        if st.event is None:
+            st.event = torch.cuda.Event()
+        st.event.record(torch.cuda.current_stream(dev))
+    result = {name: out[at:at + nbytes].view(dtype).view(shape) for name, shape, dtype, at, nbytes in st.outputs}
+    return (result, st) if return_staging else result
+
+
 # ----------------------------------------------------------------------------- normals
 RMSE_MASK_NONE, RMSE_MASK_GIVEN, RMSE_MASK_FROM_TARGET = 0, 1, 2
 

@@ -639,3 +639,63 @@ def multiscale_input_digest(inp: Dict) -> str:
     return input_digest(*(inp[k] for k in MULTISCALE_SPATIAL_KEYS), inp['scene'],
                         inp['semantic_classes_is_thing'], inp['estimate'],
                         np.frombuffer(angles.encode(), dtype=np.uint8))
+
+
+# ---- batch augmentation (data/preprocessing/{crop,flip,normalize,torch}.py) ----------------------
+# recipe -> (B, n_classes, H, W, random instances per image, crop h, crop w, flip p, depth dtype,
+#            depth mean, depth std, raw_depth, inputs of)
+AUGMENT_RECIPES = {
+    'A': (4, 9, 41, 67, 10, 37, 50, 0.5, 'uint16', 2841.94941272766, 1417.2594281672277, False, 'A'),  # w % 4 == 2
+    'B': (2, 9, 33, 64, 8, 33, 64, 1.0, 'uint16', 2841.94941272766, 1417.2594281672277, True, 'B'),    # crop == image, all flipped
+    'C': (3, 9, 20, 23, 6, 5, 7, 0.0, 'float32', 1.5, 0.75, True, 'C'),       # float32 depth with invalid values kept
+    'C1': (3, 9, 20, 23, 6, 1, 1, 0.0, 'float32', 1.5, 0.75, True, 'C'),      # the same inputs, a 1 x 1 crop
+    'D': (2, 9, 40, 301, 12, 33, 263, 0.5, 'uint16', 2841.94941272766, 1417.2594281672277, False, 'D'),  # long odd rows
+    'E': (4, 9, 21, 76, 8, 16, 68, 0.5, 'uint16', 2841.94941272766, 1417.2594281672277, True, 'E'),    # w % 4 == 0, offsets of any parity
+}
+AUGMENT_SPATIAL_KEYS = ('rgb', 'depth', 'semantic', 'instance', 'normal', 'valid', 'segment_ids')
+
+
+def make_augment_inputs(recipe: str, seed: int) -> Dict:
+    """A collated RAW batch as the dataset yields it, channels last: `rgb` u8 [B,H,W,3] covering 0
+    and 255, `depth` [B,H,W] — u16 covering 0 and 65535, or f32 with 0.0, -0.0, the recipe's
+    mean (normalises to 0) and NaN strewn in —, `semantic` u8, `instance` i32 and `valid` bool
+    [B,H,W], `normal` f32 [B,H,W,3] with the NaN payloads, -0.0, infinities and denormals of
+    `make_multiscale_inputs`, `segment_ids` u32 [B,H,W] above 2^16 (the device batch holds it as
+    i64) and `orientations`, one dict {instance id: angle} per image."""
+    B, C, H, W, n_inst, _, _, _, depth_dtype, depth_mean = AUGMENT_RECIPES[AUGMENT_RECIPES[recipe][12]][:10]
+    maps = make_label_maps(B, C, H, W, n_instances=n_inst, seed=seed, max_radius=max(4, min(H, W) // 3))
+    sem, ins = maps['semantic'], maps['instance']
+    rng = np.random.default_rng(seed + 15485863)
+    rgb = rng.integers(0, 256, (B, H, W, 3)).astype(np.uint8)
+    rgb[rng.random(rgb.shape) < 0.05] = 0
+    rgb[rng.random(rgb.shape) < 0.05] = 255
+    if depth_dtype == 'uint16':
+        depth = rng.integers(0, 65536, (B, H, W)).astype(np.uint16)
+        depth[rng.random(depth.shape) < 0.1] = 0
+        depth[rng.random(depth.shape) < 0.05] = 65535
+    else:
+        depth = (rng.random((B, H, W)) * 4.0).astype(np.float32)
+        kind = rng.integers(0, 10, depth.shape)
+        for k, bits in enumerate((0x00000000, 0x80000000, np.float32(depth_mean).view(np.uint32), 0x7fc00000)):
+            depth.view(np.uint32)[kind == k] = bits
+    normal = rng.standard_normal((B, H, W, 3)).astype(np.float32)
+    bits = normal.view(np.uint32)
+    special = np.array([0x7fc00000, 0xffc00001, 0x7f800123, 0x80000000, 0x00000000, 0x7f800000,
+                        0xff800000, 0x00000001, 0x807fffff], np.uint32)
+    strewn = rng.random(normal.shape) < 0.2
+    bits[strewn] = rng.choice(special, size=int(strewn.sum()))
+    valid = rng.random((B, H, W)) < 0.5
+    segment_ids = (sem.astype(np.uint32) << 16) + ins.astype(np.uint32) + np.uint32(0x80000000) * \
+        (rng.random((B, H, W)) < 0.25)
+    orientations = [{int(i): float(rng.uniform(0.0, 2.0 * np.pi)) for i in np.unique(ins[b]) if i != 0}
+                    for b in range(B)]
+    return {'rgb': rgb, 'depth': depth, 'semantic': sem, 'instance': ins, 'normal': normal, 'valid': valid,
+            'segment_ids': segment_ids, 'orientations': orientations,
+            'semantic_classes_is_thing': maps['semantic_classes_is_thing']}
+
+
+def augment_input_digest(inp: Dict) -> str:
+    """SHA-256 over everything `make_augment_inputs` returns (fixture and tests compare it)"""
+    angles = json.dumps([[[int(k), float(v)] for k, v in d.items()] for d in inp['orientations']])
+    return input_digest(*(inp[k] for k in AUGMENT_SPATIAL_KEYS), inp['semantic_classes_is_thing'],
+                        np.frombuffer(angles.encode(), dtype=np.uint8))
