@@ -993,6 +993,43 @@ typedef struct nmsa_augment_desc {
 int nmsa_batch_augment(void* staging_host, void* staging_device, int n_desc, int n_samples,
                        int n_words, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * scene classification (csrc/scene.hip)
+ *
+ * nmsa_scene_step: the scene task's whole step in ONE launch of one workgroup — softmax score and
+ *   argmax (model/postprocessing/scene.py:42-44), the loss and its gradient (task_helper/scene.py:
+ *   37-42, 61-63: torch.nn.CrossEntropyLoss(weight, label_smoothing, ignore_index=-1,
+ *   reduction='mean') on labels - 1) and the confusion-matrix update (scene.py:104-108).
+ *   logits        [B, C] contiguous, NMSA_F32 | NMSA_BF16 | NMSA_F16; 1 <= C <=
+ *                 NMSA_SCENE_MAX_CLASSES, B >= 1.  Values are promoted exactly; the row arithmetic
+ *                 is float64 and every output is rounded once to its type.
+ *   labels        [B], NMSA_U8 | NMSA_I32 | NMSA_I64, or NULL: batch['scene'], 0 = void, class c
+ *                 is label c + 1.  A label outside 0..C raises NMSA_ST_VALUE_RANGE in `status`
+ *                 and its row is treated as void.
+ *   class_weights float [C] or NULL; label_smoothing in [0, 1]: as torch.nn.CrossEntropyLoss.
+ *   Outputs, each may be NULL (= not wanted, nothing is written for it):
+ *   score    float [B]    max(softmax(logits, dim=1))
+ *   idx      i64 [B]      index of the largest logit, the first one among equal logits
+ *   loss     float [3]    numerator (sum of the rows' weighted terms), divisor (sum of
+ *                         w[target] over the non-void rows, their count without weights) and the
+ *                         quotient, which is the loss; no non-void row: 0 / 0 = NaN, as torch
+ *   grad     [B, C] in the logits' dtype: d loss / d logits for an upstream gradient of 1; zero
+ *                         in void rows
+ *   confmat  i64 [C, C]   ACCUMULATED: confmat[label - 1, idx] += 1 for every non-void row
+ *   status   i32 [1]      device word, OR-ed with NMSA_ST_VALUE_RANGE
+ *   loss, grad and confmat need labels.  Deterministic: a fixed order of summation, no float
+ *   atomics.  No workspace, no host synchronisation; capturable in a hipGraph (a replay adds to
+ *   `confmat` again).  Everything is checked before anything is enqueued, with or without a
+ *   device: NMSA_ERR_ARG for NULL logits, B < 1, C outside 1..NMSA_SCENE_MAX_CLASSES, a
+ *   label_smoothing outside [0, 1] (NaN included), loss / grad / confmat without labels;
+ *   NMSA_ERR_UNSUPPORTED for any other logits_dtype or (with labels) label_dtype.
+ * ------------------------------------------------------------------------- */
+#define NMSA_SCENE_MAX_CLASSES 4096
+int nmsa_scene_step(const void* logits, int logits_dtype, const void* labels, int label_dtype,
+                    int B, int C, const float* class_weights, float label_smoothing,
+                    float* score, int64_t* idx, float* loss, void* grad, int64_t* confmat,
+                    int32_t* status, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'nmsa.h')
 
 NMSA_F32, NMSA_BF16, NMSA_F16 = 0, 1, 2
 NMSA_U8, NMSA_I16, NMSA_I32, NMSA_I64 = 0, 1, 2, 3
+# include/nmsa.h: status bit of a value outside its range; class limit of nmsa_scene_step
+NMSA_ST_VALUE_RANGE = 8
+NMSA_SCENE_MAX_CLASSES = 4096
 
 
 class NmsaError(RuntimeError):
@@ -98,6 +101,7 @@ _SIGNATURES = {
                                       _i, _vp, _vp, _vp, _vp]),
     'nmsa_multiscale_nearest': (_i, [_vp, _vp, _i, _i, _vp]),
     'nmsa_batch_augment': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'nmsa_scene_step': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -1,6 +1,7 @@
 """Losses of the hot path (reference loss/__init__.py)."""
 from .base import LossBase
 from .ce import CrossEntropyLossSemantic
+from .ce_scene import CrossEntropyLossScene
 from .cos_emb import CosineEmbeddingLoss
 from .focal import CenterFocalLoss
 from .l1 import L1Loss

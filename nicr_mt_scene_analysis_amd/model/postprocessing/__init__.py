@@ -4,8 +4,9 @@ On the hot path: 'semantic', 'instance', 'panoptic' and 'dense-visual-embedding'
 normalisation + projection onto the class embeddings on HIP, class maps through the semantic
 path).  `NormalPostprocessing` exists as a class (lazy nearest resize to the dataset resolution)
 but is not registered here yet: the factory still raises NotImplementedError for 'normal', which
-an existing test pins; registering it is a follow-up that flips that assertion.  'scene' is
-another task's postprocessor (softmax) and out of scope of this package."""
+an existing test pins; registering it is a follow-up that flips that assertion.  The same holds
+for 'scene': `ScenePostprocessing` (softmax score and index of the [B, C] logits in one launch)
+exists as a class and is used directly; the factory keeps raising for the name."""
 from typing import Any
 
 from ...utils import partial_class
@@ -15,6 +16,7 @@ from .dense_visual_embedding import DenseVisualEmbeddingPostprocessing
 from .instance import InstancePostprocessing
 from .normal import NormalPostprocessing
 from .panoptic import PanopticPostprocessing
+from .scene import ScenePostprocessing
 from .semantic import SemanticPostprocessing
 
 _OUT_OF_SCOPE = ('normal', 'scene')

@@ -1055,6 +1055,84 @@ def rmse_update(sum_state: torch.Tensor, count_state: torch.Tensor, preds: torch
         L.ptr(sum_state), L.ptr(count_state), L.stream_ptr(t.device)), 'nmsa_rmse_update')
 
 
+# ----------------------------------------------------------------------------- scene
+_SCENE_OUTPUTS = ('score', 'idx', 'loss', 'grad')
+
+
+def scene_step(logits: torch.Tensor, labels: Optional[torch.Tensor] = None,
+               class_weights: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
+               want: Sequence[str] = ('score', 'idx'), confmat: Optional[torch.Tensor] = None,
+               status: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The scene task's step in one launch (include/nmsa.h nmsa_scene_step), no host sync.
+    `logits` [B, C] float32 / bfloat16 / float16; `labels` [B] uint8 / int32 / int64 in the form of
+    batch['scene'] (0 = void, class c is c + 1) or None.  `want` names the outputs to allocate and
+    return: 'score' float32 [B] and 'idx' int64 [B] (reference model/postprocessing/scene.py:42-44),
+    'loss' float32 [3] = (numerator, divisor, loss) of torch.nn.CrossEntropyLoss(class_weights,
+    label_smoothing, ignore_index=-1, reduction='mean') on labels - 1, 'grad' [B, C] in the
+    logits' dtype = d loss / d logits.  `confmat` int64 [C, C] is ADDED into (row = label - 1,
+    column = idx) and returned as given.  `status` int32 [1] (allocated when labels are given and
+    none is passed) collects L.NMSA_ST_VALUE_RANGE for labels outside 0..C, whose rows count as void."""
+    want = tuple(want)
+    unknown = [w for w in want if w not in _SCENE_OUTPUTS]
+    if unknown:
+        raise ValueError(f'unknown outputs {unknown}; known: {_SCENE_OUTPUTS}')
+    code = L.float_dtype_code(logits)               # TypeError for anything but f32 / bf16 / f16
+    _require_on_device(logits, 'logits')
+    if logits.ndim != 2:
+        raise ValueError(f'logits must be [B, C], got shape {tuple(logits.shape)}')
+    B, C = (int(n) for n in logits.shape)
+    if B < 1 or not 1 <= C <= L.NMSA_SCENE_MAX_CLASSES:
+        raise ValueError(f'B >= 1 and 1 <= C <= {L.NMSA_SCENE_MAX_CLASSES} are supported, got B={B}, C={C}')
+    if not 0.0 <= float(label_smoothing) <= 1.0:
+        raise ValueError(f'label_smoothing must be in [0, 1], got {label_smoothing}')
+    x, dev = logits.detach().contiguous(), logits.device
+    lab, lab_code = None, 0
+    if labels is not None:
+        _require_on_device(labels, 'labels')
+        if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
+            raise TypeError(f'labels must be uint8, int32 or int64, got {labels.dtype}')
+        if tuple(labels.shape) != (B,):
+            raise ValueError(f'labels must be [B] = [{B}], got shape {tuple(labels.shape)}')
+        lab, lab_code = labels.contiguous(), L.int_dtype_code(labels)
+    elif 'loss' in want or 'grad' in want or confmat is not None:
+        raise ValueError('loss, grad and confmat need labels')
+    w = None
+    if class_weights is not None:
+        _require_on_device(class_weights, 'class_weights')
+        if class_weights.dtype != torch.float32 or tuple(class_weights.shape) != (C,):
+            raise TypeError(f'class_weights must be float32 [{C}], got {class_weights.dtype} '
+                            f'{tuple(class_weights.shape)}')
+        w = class_weights.contiguous()
+    if confmat is not None:
+        _require_on_device(confmat, 'confmat')
+        if confmat.dtype != torch.int64 or tuple(confmat.shape) != (C, C) or not confmat.is_contiguous():
+            raise TypeError(f'confmat must be a contiguous int64 [{C}, {C}] tensor')
+    if status is not None:
+        _require_on_device(status, 'status')
+        if status.dtype != torch.int32 or status.numel() != 1:
+            raise TypeError('status is one int32 word')
+    elif lab is not None:
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    out = {}
+    if 'score' in want:
+        out['score'] = torch.empty((B,), dtype=torch.float32, device=dev)
+    if 'idx' in want:
+        out['idx'] = torch.empty((B,), dtype=torch.int64, device=dev)
+    if 'loss' in want:
+        out['loss'] = torch.empty((3,), dtype=torch.float32, device=dev)
+    if 'grad' in want:
+        out['grad'] = torch.empty((B, C), dtype=x.dtype, device=dev)
+    L.check(L.lib().nmsa_scene_step(
+        L.ptr(x), code, L.ptr(lab), lab_code, B, C, L.ptr(w), float(label_smoothing),
+        L.ptr(out.get('score')), L.ptr(out.get('idx')), L.ptr(out.get('loss')), L.ptr(out.get('grad')),
+        L.ptr(confmat), L.ptr(status), L.stream_ptr(dev)), 'nmsa_scene_step')
+    if confmat is not None:
+        out['confmat'] = confmat
+    if status is not None:
+        out['status'] = status
+    return out
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""

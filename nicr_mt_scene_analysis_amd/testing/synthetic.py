@@ -699,3 +699,47 @@ def augment_input_digest(inp: Dict) -> str:
     angles = json.dumps([[[int(k), float(v)] for k, v in d.items()] for d in inp['orientations']])
     return input_digest(*(inp[k] for k in AUGMENT_SPATIAL_KEYS), inp['semantic_classes_is_thing'],
                         np.frombuffer(angles.encode(), dtype=np.uint8))
+
+
+# ----------------------------------------------------------------------------- scene task
+# name: (n_classes, class weights, label smoothing, seed) of tests/golden/scene_task.npz
+SCENE_CASES = {'plain': (10, False, 0.0, 70), 'weighted': (10, True, 0.0, 71),
+               'smoothed': (45, False, 0.1, 72), 'weighted_smoothed': (45, True, 0.1, 73)}
+SCENE_EPOCHS = 2
+# the batches of every epoch: (rows, kind)
+SCENE_BATCHES = ((8, 'plain'), (6, 'some_void'), (4, 'all_void'), (7, 'ties'))
+
+
+def _scene_batch(rng, B: int, C: int, kind: str):
+    logits = (rng.standard_normal((B, C)) * 3.0).astype(np.float32)
+    labels = rng.integers(1, C + 1, size=(B,)).astype(np.int64)
+    hit = rng.random(B) < 0.6                   # a head that is right more often than chance
+    logits[hit, labels[hit] - 1] += np.float32(6.0)
+    if kind == 'some_void':
+        labels[rng.choice(B, size=B // 2, replace=False)] = 0
+    elif kind == 'all_void':
+        labels[:] = 0
+    elif kind == 'ties':
+        for r in range(0, B, 2):                # every other row: two or three equal largest logits
+            cols = rng.choice(C, size=2 + r % 2, replace=False)
+            logits[r, cols] = logits[r].max() + np.float32(0.5)
+    return logits, labels
+
+
+def make_scene_inputs(name: str) -> Dict[str, object]:
+    """The inputs of one case of SCENE_CASES: 'weights' (float32 [C] or None) and 'batches', a
+    list over the epochs of lists of (logits float32 [B, C], labels int64 [B], 0 = void) per
+    SCENE_BATCHES.  Generator draws and elementwise float32 arithmetic only, so the bytes are the
+    same on every host."""
+    C, weighted, _, seed = SCENE_CASES[name]
+    rng = np.random.default_rng(seed)
+    weights = (rng.random(C) + 0.25).astype(np.float32) if weighted else None
+    batches = [[_scene_batch(rng, B, C, kind) for B, kind in SCENE_BATCHES] for _ in range(SCENE_EPOCHS)]
+    return {'weights': weights, 'batches': batches}
+
+
+def scene_input_digest(inputs) -> str:
+    arrays = [a for epoch in inputs['batches'] for pair in epoch for a in pair]
+    if inputs['weights'] is not None:
+        arrays.append(inputs['weights'])
+    return input_digest(*arrays)
