@@ -284,8 +284,12 @@ int nmsa_instance_orientation_wide(const float* orientation, const void* instanc
  *     dataloader workers).  Label maps in their on-wire dtypes (data/preprocessing/torch.py:60-66:
  *     semantic uint8, instance uint16 -> int32); instance ids in [0, 65535], at most
  *     `max_instances` (<= 4096) distinct ids per image.
- *  status bits (OR-ed into *status): 1 too many distinct ids, 32 id out of range,
- *     64 semantic label outside [0, n_classes), 128 id table (max_segments) overflow.
+ *  status bits (OR-ed into *status): 1 too many distinct ids (more non-zero ids in one image than
+ *     `cap` = max_instances rounded up to a multiple of 1024: the tables are sized by cap, so the
+ *     bit starts at cap + 1 ids, not at max_instances + 1), 32 id out of range (negative ids of
+ *     the signed dtypes included), 64 semantic label outside [0, n_classes) on a pixel that carries
+ *     an instance id, 128 id table overflow (an image has more (instance, class) segments than
+ *     max_segments; n_ids is then max_segments and the lists hold the first max_segments).
  *  workspace: nmsa_targets_workspace_bytes(B, n_classes, max_instances), 8-byte aligned (16-byte
  *     aligned for the one-launch front end of the on-wire layout, see below).
  *     workspace_is_clean (nmsa_instance_targets / nmsa_panoptic_targets): 1 = this very workspace
@@ -331,8 +335,38 @@ int nmsa_instance_orientation_wide(const float* orientation, const void* instanc
  *     launches: the scan of nmsa_instance_targets (or memset + 4 on any other layout) + one paint
  *     launch (k_ot_paint: ids looked up in the scan's id table; NMSA_OT_LOOKUP=search, read per call:
  *     binary search over the keys in LDS); no host synchronisation, no allocation.
+ *
+ *  nmsa_targets_route: which kernels the three generators run for these arguments, as a mask of
+ *     NMSA_TG_ROUTE_* bits, or a negative NMSA_ERR_* for arguments the generators refuse.  The
+ *     dispatchers switch on the same predicates and on nothing else; the pointers are only looked
+ *     at for NULL and alignment, nothing is launched and no device is touched.
+ *       SCAN          the one-launch front end (k_tg_scan) of all three generators; the status word
+ *                     is then SET and the workspace left clean.  Without it: memset + the classic
+ *                     launches (presence, rank, statistics, decide / naive ranks)
+ *       FAST_LOADERS  the front end loads 4 labels per thread with one 16-byte and one 4-byte load
+ *                     (semantic uint8 4-byte aligned, instance int32 16-byte aligned, H*W % 4 == 0);
+ *                     always set with SCAN
+ *       PAINT_TILED   nmsa_instance_targets paints 128 x 16 pixel tiles (FAST_LOADERS labels,
+ *                     W % 4 == 0, center / offset 16-byte and foreground / center_mask 4-byte aligned)
+ *       PAINT_VECTOR  ... 1024 consecutive pixels per workgroup with vector stores (the same without
+ *                     W % 4 == 0: a group of 4 pixels may straddle a row end); neither bit: per element
+ *       LUT_LDS       the paint keeps the heat-map table in LDS (2*(3*sigma+1)^2 + 1 <= 4096 entries:
+ *                     sigma <= 14); without it the table is read from global memory
+ *       SCAN_16       the scan keeps 16 table slots per thread instead of 4 (max_instances > 1024)
+ *     sigma, center, offset, foreground, center_mask only matter to the paint bits (the outputs
+ *     may be NULL: counted as aligned); workspace only to SCAN (16-byte aligned; NULL: aligned).
  * ------------------------------------------------------------------------- */
+#define NMSA_TG_ROUTE_SCAN 1
+#define NMSA_TG_ROUTE_FAST_LOADERS 2
+#define NMSA_TG_ROUTE_PAINT_TILED 4
+#define NMSA_TG_ROUTE_PAINT_VECTOR 8
+#define NMSA_TG_ROUTE_LUT_LDS 16
+#define NMSA_TG_ROUTE_SCAN_16 32
 size_t nmsa_targets_workspace_bytes(int B, int n_classes, int max_instances);
+int nmsa_targets_route(const void* semantic, int sem_dtype, const void* instance, int ins_dtype,
+                       int n_classes, int H, int W, int sigma, int max_instances,
+                       const float* center, const void* offset, const uint8_t* foreground,
+                       const uint8_t* center_mask, const void* workspace);
 int nmsa_instance_clear_stuff(const void* semantic, int sem_dtype, void* instance, int ins_dtype,
                               const uint8_t* is_stuff_class, int n_classes, int64_t n_px,
                               nmsa_stream_t stream);

@@ -25,6 +25,9 @@ NMSA_U8, NMSA_I16, NMSA_I32, NMSA_I64 = 0, 1, 2, 3
 # include/nmsa.h: status bit of a value outside its range; class limit of nmsa_scene_step
 NMSA_ST_VALUE_RANGE = 8
 NMSA_SCENE_MAX_CLASSES = 4096
+# include/nmsa.h: bits of nmsa_targets_route
+(NMSA_TG_ROUTE_SCAN, NMSA_TG_ROUTE_FAST_LOADERS, NMSA_TG_ROUTE_PAINT_TILED, NMSA_TG_ROUTE_PAINT_VECTOR,
+ NMSA_TG_ROUTE_LUT_LDS, NMSA_TG_ROUTE_SCAN_16) = 1, 2, 4, 8, 16, 32
 
 
 class NmsaError(RuntimeError):
@@ -80,6 +83,7 @@ _SIGNATURES = {
     'nmsa_panoptic_scores': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64,
                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nmsa_targets_workspace_bytes': (_sz, [_i, _i, _i]),
+    'nmsa_targets_route': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'nmsa_instance_clear_stuff': (_i, [_vp, _i, _vp, _i, _vp, _i, _i64, _vp]),
     'nmsa_instance_targets': (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),

@@ -563,11 +563,17 @@ __device__ __forceinline__ void tg_rank_decide_tail(
     }
     __syncthreads();                                     // (bitmap + prefix in LDS are dead from here)
     TG_STAMP(5);
-    // the ids by dense rank, kept in the dead prefix words (up to 2048 ranks; beyond: the table)
+    // the ids by dense rank, kept in the dead prefix words (up to 2048 ranks; beyond: the table) —
+    // unless the naive merge needs those words: its u16 rank cells fill the bitmap words first and
+    // grow into the prefix words once an image has more than 4096 of them; the ids then all come
+    // from the table
+    const bool cells_on_ids = !WITH_MOMENTS && n_dense * NC > 2 * MW_WORDS && n_dense * NC <= TGS_CELLS_LDS;
     int* s_id = (int*)s_prefix;
+    if (!cells_on_ids) {
 #pragma unroll
-    for (int k = 0; k < KPT; ++k) if (rank_of_key[k] >= 0 && rank_of_key[k] < MW_WORDS) s_id[rank_of_key[k]] = key[k];
-    auto id_of = [&](int d) -> int { return d < MW_WORDS ? s_id[d] : ld_shared(&h.hkeys[s_slot[d]]); };
+        for (int k = 0; k < KPT; ++k) if (rank_of_key[k] >= 0 && rank_of_key[k] < MW_WORDS) s_id[rank_of_key[k]] = key[k];
+    }
+    auto id_of = [&](int d) -> int { return (!cells_on_ids && d < MW_WORDS) ? s_id[d] : ld_shared(&h.hkeys[s_slot[d]]); };
     bool handed_over = false;
     if (WITH_MOMENTS) {
         // every status bit of this image is known (the overflow bit above was this tail's last):
@@ -959,6 +965,7 @@ __global__ __launch_bounds__(256) void k_tg_scan(
 constexpr int TGP_THREADS = 256;
 constexpr int TGP_PX = 1024;                 // consecutive pixels per workgroup
 constexpr int TGP_LUT_LDS = 4096;            // heat-map table entries kept in LDS (sigma <= 14)
+__host__ __device__ inline bool tg_lut_in_lds(int lut_n) { return lut_n <= TGP_LUT_LDS; }
 
 template <bool NORMALIZED, bool FAST>
 __global__ __launch_bounds__(TGP_THREADS) void k_tg_paint(
@@ -976,7 +983,7 @@ __global__ __launch_bounds__(TGP_THREADS) void k_tg_paint(
     const int n_enc = v.counters[1];
     int* s_cand = tg_lds;
     float* s_lut = (float*)(tg_lds + 2 * cap);
-    const bool lut_in_lds = lut_n <= TGP_LUT_LDS;
+    const bool lut_in_lds = tg_lut_in_lds(lut_n);
 
     const int p_begin = blockIdx.x * TGP_PX;
     const int p_end = min(p_begin + TGP_PX, P);
@@ -1124,7 +1131,7 @@ __global__ __launch_bounds__(TGP_THREADS) void k_tg_paint_tile(
     TgView v = tg_view(ws, b, cap, NC);
     int* s_cand = tg_lds;
     float* s_lut = (float*)(tg_lds + 2 * cap);
-    const bool lut_in_lds = lut_n <= TGP_LUT_LDS;
+    const bool lut_in_lds = tg_lut_in_lds(lut_n);
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int x = tx * TGT_W + (threadIdx.x & 31) * 4;
     // a thread owns G groups of 4 pixels, TGT_ROWS rows apart: their label loads and the dependent
@@ -1706,6 +1713,43 @@ bool tg_scan_ok(const void* sem, int sem_dtype, const void* ins, int ins_dtype, 
     return tg_fast(sem, sem_dtype, ins, ins_dtype, P) && W % 4 == 0 && NC <= TGF_MAX_NC;
 }
 
+// ---- THE route rules: the dispatchers below switch on these answers and on nothing else, and
+// nmsa_targets_route exports them (NMSA_TG_ROUTE_* of include/nmsa.h) -------------------------------
+// the scan's table slots per thread: 4 up to 1024 table slots, 16 beyond
+bool tg_scan_small(int cap) { return tg_hash_slots(cap) <= 1024; }
+
+// front end of the three generators: the one-launch scan, or the classic launches with the
+// vectorised (FAST) or the per-element label loaders
+int tg_front_route(const void* sem, int sem_dtype, const void* ins, int ins_dtype, int P, int W, int NC,
+                   int cap, const void* ws)
+{
+    if (tg_scan_ok(sem, sem_dtype, ins, ins_dtype, P, W, NC) && (uintptr_t)ws % 16 == 0)
+        return NMSA_TG_ROUTE_SCAN | NMSA_TG_ROUTE_FAST_LOADERS | (tg_scan_small(cap) ? 0 : NMSA_TG_ROUTE_SCAN_16);
+    return tg_fast(sem, sem_dtype, ins, ins_dtype, P) ? NMSA_TG_ROUTE_FAST_LOADERS : 0;
+}
+
+int tg_lut_entries(int sigma) { const int radius = 3 * sigma + 1; return 2 * radius * radius + 1; }
+
+// groups of 4 pixels per thread of the tiled paint; NMSA_TG_PAINT_TILED=0: never tiled
+int tg_paint_tiled_groups()
+{
+    static const int tiled = getenv("NMSA_TG_PAINT_TILED") ? atoi(getenv("NMSA_TG_PAINT_TILED")) : 2;
+    return tiled >= 4 ? 4 : tiled >= 2 ? 2 : tiled ? 1 : 0;
+}
+
+// paint of nmsa_instance_targets: 2-d tiles, 1024 consecutive pixels with vector stores, or per
+// element; the heat-map table in LDS or read from global memory
+int tg_paint_route(const void* sem, int sem_dtype, const void* ins, int ins_dtype, int P, int W, int sigma,
+                   const void* center, const void* offset, const void* foreground, const void* center_mask)
+{
+    const bool fast = tg_fast(sem, sem_dtype, ins, ins_dtype, P) &&
+                      (uintptr_t)center % 16 == 0 && (uintptr_t)offset % 16 == 0 &&
+                      (uintptr_t)foreground % 4 == 0 && (uintptr_t)center_mask % 4 == 0;
+    const int lut = tg_lut_in_lds(tg_lut_entries(sigma)) ? NMSA_TG_ROUTE_LUT_LDS : 0;
+    if (fast && tg_paint_tiled_groups() && W % 4 == 0) return lut | NMSA_TG_ROUTE_PAINT_TILED;
+    return lut | (fast ? NMSA_TG_ROUTE_PAINT_VECTOR : 0);
+}
+
 size_t tg_scan_lds_bytes(int cap, bool moments)
 {
     // scratch | bitmap + prefix | slot u16 [cap] | enc u8 [cap] (instance targets) or base i32 [cap] (naive merge)
@@ -1764,7 +1808,8 @@ int tg_common(const void* sem, int sem_dtype, const void* ins, int ins_dtype, in
               int32_t* n_ids = nullptr, bool* did_tail = nullptr, int workspace_is_clean = 0)
 {
     if (did_tail) *did_tail = false;
-    if (tg_scan_ok(sem, sem_dtype, ins, ins_dtype, P, W, NC) && (uintptr_t)ws % 16 == 0) {
+    const int route = tg_front_route(sem, sem_dtype, ins, ins_dtype, P, W, NC, cap, ws);
+    if (route & NMSA_TG_ROUTE_SCAN) {
         // ONE launch behind a memset of the hash tables (k_tg_scan: scan + rank + decide / naive ranks)
         unsigned char* hs = ws + (size_t)B * tg_image_bytes(cap, NC);
         // a workspace the previous call left behind is all zero again (the tails clean what the
@@ -1773,7 +1818,7 @@ int tg_common(const void* sem, int sem_dtype, const void* ins, int ins_dtype, in
         int rc = NMSA_OK;
         if (!workspace_is_clean && (rc = tg_zero(hs, hbytes, stream))) return rc;
         const size_t lds = tg_scan_lds_bytes(cap, moments);
-        const bool small = tg_hash_slots(cap) <= 1024;
+        const bool small = !(route & NMSA_TG_ROUTE_SCAN_16);
         // ONE round of resident workgroups: what the registers and the LDS of this instantiation admit
         int resident = 0;
         {
@@ -1803,7 +1848,7 @@ int tg_common(const void* sem, int sem_dtype, const void* ins, int ins_dtype, in
     int rc = tg_zero(ws, (size_t)B * tg_image_bytes(cap, NC), stream);
     if (rc) return rc;
     const int gx = tg_grid_x(P);
-    const bool fast = tg_fast(sem, sem_dtype, ins, ins_dtype, P);
+    const bool fast = (route & NMSA_TG_ROUTE_FAST_LOADERS) != 0;
     if (fast)
         hipLaunchKernelGGL(k_tg_presence<true>, dim3(gx, B), dim3(256), 0, stream, ins, ins_dtype, P, cap,
                            NC, ws, status);
@@ -1835,6 +1880,24 @@ extern "C" size_t nmsa_targets_workspace_bytes(int B, int n_classes, int max_ins
     // [ dense per-image tables (TgView) | per-image hash tables of the one-launch front end (TgHash) ]
     const int cap = tg_cap(max_instances);
     return (size_t)B * (tg_image_bytes(cap, n_classes) + tg_hash_bytes(cap, n_classes)) + TG_GLOBAL_BYTES;
+}
+
+extern "C" int nmsa_targets_route(const void* semantic, int sem_dtype, const void* instance, int ins_dtype,
+                                  int n_classes, int H, int W, int sigma, int max_instances,
+                                  const float* center, const void* offset, const uint8_t* foreground,
+                                  const uint8_t* center_mask, const void* workspace)
+{
+    if (!semantic || !instance) return NMSA_ERR_ARG;
+    if (H <= 0 || W <= 0 || H > 32767 || W > 32767 || (int64_t)H * W > ((int64_t)1 << 30)) return NMSA_ERR_ARG;
+    if (n_classes <= 0 || n_classes > 65536 || sigma <= 0 || sigma > 64) return NMSA_ERR_ARG;
+    if (max_instances <= 0 || max_instances > 4096) return NMSA_ERR_ARG;
+    if (tg_bad_dtype(sem_dtype) || tg_bad_dtype(ins_dtype)) return NMSA_ERR_ARG;
+    if ((uintptr_t)workspace % 8) return NMSA_ERR_ARG;
+    const int P = H * W;
+    return tg_front_route(semantic, sem_dtype, instance, ins_dtype, P, W, n_classes, tg_cap(max_instances),
+                          workspace) |
+           tg_paint_route(semantic, sem_dtype, instance, ins_dtype, P, W, sigma, center, offset, foreground,
+                          center_mask);
 }
 
 extern "C" int nmsa_instance_targets(const void* semantic, int sem_dtype, const void* instance,
@@ -1875,23 +1938,22 @@ extern "C" int nmsa_instance_targets(const void* semantic, int sem_dtype, const 
         if ((rc = check_launch())) return rc;
     }
     const int radius = 3 * sigma + 1;
-    const int lut_n = 2 * radius * radius + 1;
-    const size_t lds = (size_t)cap * 2 * sizeof(int) + (lut_n <= TGP_LUT_LDS ? (size_t)lut_n * 4 : 0);
+    const int lut_n = tg_lut_entries(sigma);
+    const int paint = tg_paint_route(semantic, sem_dtype, instance, ins_dtype, P, W, sigma, center, offset,
+                                     foreground, center_mask);
+    const size_t lds = (size_t)cap * 2 * sizeof(int) + ((paint & NMSA_TG_ROUTE_LUT_LDS) ? (size_t)lut_n * 4 : 0);
     dim3 grid((P + TGP_PX - 1) / TGP_PX, B);
-    const bool fast = tg_fast(semantic, sem_dtype, instance, ins_dtype, P) &&
-                      (uintptr_t)center % 16 == 0 && (uintptr_t)offset % 16 == 0 &&
-                      (uintptr_t)foreground % 4 == 0 && (uintptr_t)center_mask % 4 == 0;
+    const bool fast = (paint & NMSA_TG_ROUTE_PAINT_VECTOR) != 0;
 #define NMSA_LAUNCH_TGP(N, F)                                                                          \
     hipLaunchKernelGGL((k_tg_paint<N, F>), grid, dim3(TGP_THREADS), lds, stream, semantic, sem_dtype,  \
                        instance, ins_dtype, is_stuff_class, gauss_lut, lut_n, radius, H, W, cap,       \
                        n_classes, ws, center, offset, foreground, center_mask)
-    static const int tiled = getenv("NMSA_TG_PAINT_TILED") ? atoi(getenv("NMSA_TG_PAINT_TILED")) : 2;
-    if (fast && tiled && W % 4 == 0) {
+    if (paint & NMSA_TG_ROUTE_PAINT_TILED) {
         // 128 x (8 G) pixel tiles, G = NMSA_TG_PAINT_TILED groups of 4 pixels per thread
-        const int G = tiled >= 4 ? 4 : tiled >= 2 ? 2 : 1;
+        const int G = tg_paint_tiled_groups();
         const int tiles_x = (W + TGT_W - 1) / TGT_W, tiles_y = (H + TGT_ROWS * G - 1) / (TGT_ROWS * G);
         const dim3 tgrid(tiles_x * tiles_y, B);
-        const size_t tlds = (size_t)cap * 2 * sizeof(int) + (lut_n <= TGP_LUT_LDS ? (size_t)lut_n * 4 : 0);
+        const size_t tlds = lds;
 #define NMSA_LAUNCH_TGT(N, GG)                                                                          \
         hipLaunchKernelGGL((k_tg_paint_tile<N, GG>), tgrid, dim3(TGP_THREADS), tlds, stream,            \
                            (const uint8_t*)semantic, (const int32_t*)instance, is_stuff_class, gauss_lut, \

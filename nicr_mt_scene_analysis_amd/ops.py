@@ -421,6 +421,23 @@ def _targets_on_wire(sem: torch.Tensor, ins: torch.Tensor, H: int, W: int, n_cla
             sem.data_ptr() % 4 == 0 and ins.data_ptr() % 16 == 0)
 
 
+def targets_route(semantic: torch.Tensor, instance: torch.Tensor, n_classes: int, sigma: int = 8,
+                  max_instances: int = 1024) -> int:
+    """The kernels `instance_targets` / `panoptic_targets` / `orientation_targets` run for these
+    label maps (`nmsa_targets_route`): a mask of `_lib.NMSA_TG_ROUTE_*` bits.  The outputs and the
+    workspace of those calls are fresh torch allocations (256-byte aligned) and go in as NULL,
+    which the query counts as aligned; nothing is launched or allocated."""
+    sem = L.require_device_tensor(semantic, 'semantic')
+    ins = L.require_device_tensor(instance, 'instance')
+    B, H, W = sem.shape
+    rc = L.lib().nmsa_targets_route(
+        L.ptr(sem), L.int_dtype_code(sem), L.ptr(ins), L.int_dtype_code(ins), int(n_classes), H, W,
+        int(sigma), int(max_instances), None, None, None, None, None)
+    if rc < 0:
+        L.check(rc, 'nmsa_targets_route')
+    return rc
+
+
 def instance_clear_stuff(semantic: torch.Tensor, instance: torch.Tensor,
                          is_stuff_class: torch.Tensor) -> torch.Tensor:
     """reference: InstanceClearStuffIDs (data/preprocessing/instance.py:46-93); in place."""

@@ -107,6 +107,21 @@ def test_bad_arguments_return_codes(env):
     assert pq(num_categories=0) == ERR_ARG
     assert pq(offset=0) == ERR_ARG
     assert pq(ws_bytes=16) == ERR_WORKSPACE
+
+    def tg_route(sem=t['u8'], sd=0, ins=t['i64'], idt=3, nc=C, h=H, w=W, sigma=8, max_inst=1024):
+        return lib.nmsa_targets_route(p(sem), sd, p(ins), idt, nc, h, w, sigma, max_inst,
+                                      p(t['center']), p(t['offset']), p(t['fg']), p(t['u8b']), p(t['ws']))
+    assert tg_route() == 16                              # uint8 / int64 labels: per element, table in LDS
+    assert tg_route(sem=None) == ERR_ARG
+    assert tg_route(ins=None) == ERR_ARG
+    assert tg_route(sd=9) == ERR_ARG
+    assert tg_route(idt=-1) == ERR_ARG
+    assert tg_route(nc=0) == ERR_ARG
+    assert tg_route(h=0) == ERR_ARG
+    assert tg_route(w=1 << 15) == ERR_ARG
+    assert tg_route(sigma=0) == ERR_ARG
+    assert tg_route(sigma=65) == ERR_ARG                 # the generators' limit
+    assert tg_route(max_inst=4097) == ERR_ARG
     torch.cuda.synchronize()                             # nothing faulted on the way
 
 

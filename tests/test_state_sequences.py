@@ -378,7 +378,9 @@ def check_target_results(oracle, c, out, sem, ins, is_thing, stuff):
                 assert status & 32, (c, what, status)
             elif c['kind'] == 'class_range':
                 assert status & 64, (c, what, status)
-            continue                    # (too_many: whatever it reports, the next call must be exact)
+            elif max(len(np.unique(ins[b][ins[b] > 0])) for b in range(B)) > -(-c['max_inst'] // 1024) * 1024:
+                assert status & 1, (c, what, status)    # more distinct ids than the tables hold
+            continue                    # (too_many within the tables: the next call must be exact)
         assert status == 0, (c, what, status)
         if what == 'instance':
             o = oracle.instance_targets(sem, ins, c['NC'], is_thing, stuff, c['sigma'], c['normalized'])
