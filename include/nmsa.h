@@ -1064,6 +1064,59 @@ int nmsa_scene_step(const void* logits, int logits_dtype, const void* labels, in
                     float* score, int64_t* idx, float* loss, void* grad, int64_t* confmat,
                     int32_t* status, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * learned x2 upsampling of the decoder heads (csrc/upsampling.hip)
+ *     model/upsampling.py:39-96, modes 'learned-3x3' (zeropad = 0) and 'learned-3x3-zeropad'
+ *     (zeropad = 1): nearest x2, replication / zero pad, depthwise 3x3 convolution.
+ *
+ *   y[n,c,Y,X] = b[c] + sum_{i,j in 0..2} W[c,0,i,j] * U(Y+i-1, X+j-1)
+ *   U(p,q)     = x[n,c,p>>1,q>>1] for 0 <= p < 2h, 0 <= q < 2w;  replicate: p, q clamped to that
+ *                range first;  zeropad: 0 outside it
+ *
+ *   x, gx      [B,C,h,w]   NMSA_F32 | NMSA_BF16 | NMSA_F16, contiguous; one dtype per call
+ *   y, gy      [B,C,2h,2w] the same dtype
+ *   weight, gweight  f32 [C,1,3,3];  bias, gbias  f32 [C] (bias may be NULL: no bias)
+ *   Products and sums are float32 (fused multiply-adds on pre-added weight pairs); a half output
+ *   is rounded once, to nearest even.
+ *
+ * nmsa_upsample2x_dw3x3_fwd: one launch, x read once, y written once, no workspace.
+ * nmsa_upsample2x_dw3x3_bwd: gx = d/dx, gweight = d/dW, gbias = d/db of sum(gy * y); each of the
+ *   three may be NULL (not wanted; all NULL: NMSA_OK after the checks, nothing is launched).  One
+ *   launch over gy and x writes gx and ten partial sums per workgroup into `workspace`; a second,
+ *   small launch sums them per channel in a fixed order.  No float atomics: two calls on the same
+ *   inputs give the same bits.  `workspace` (16-byte aligned, at least
+ *   nmsa_upsample2x_dw3x3_bwd_workspace_bytes(B, C, h, w) bytes, any dtype) is needed only with
+ *   gweight or gbias; its contents are scratch.
+ * nmsa_upsample2x_dw3x3_route (host only, nothing is launched, no device is touched): the route a
+ *   call with these two tensors takes.  NMSA_UP_ROUTE_VECTOR: a lane owns 2 (f32) or 4 (half)
+ *   consecutive input pixels and moves 16-byte vectors; taken when w % 2 == 0 (f32) / w % 4 == 0
+ *   (half) and EVERY tensor of the call (x and y; gy, x and gx) starts on 16 bytes.
+ *   NMSA_UP_ROUTE_PIXEL: one input pixel per lane, element-wise accesses, any width and any
+ *   element-aligned pointer.  `x` is an input-sized tensor of the call, `y_or_gx` another of its
+ *   tensors (forward: y; backward: gx, and once more with gy — the call takes the vector route
+ *   when every answer is NMSA_UP_ROUTE_VECTOR).
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a
+ * NULL x / y / gy / weight, a dtype other than the three, B, C, h or w below 1, zeropad other than
+ * 0 / 1, a pointer that is not aligned to its element, a NULL or misaligned workspace where one is
+ * needed.  NMSA_ERR_WORKSPACE: a workspace that is too small.  NMSA_ERR_UNSUPPORTED: a single
+ * output plane of 2^31 elements or more (4hw; offsets inside a plane are 32-bit, the plane base is
+ * 64-bit, so B*C*4hw may exceed 2^31), B*C above 2^31 - 1, 2^31 or more workgroup items.  No host
+ * synchronisation, no allocation; capturable in a hipGraph as a single chain.
+ * ------------------------------------------------------------------------- */
+#define NMSA_UP_ROUTE_VECTOR 1
+#define NMSA_UP_ROUTE_PIXEL 2
+int nmsa_upsample2x_dw3x3_route(const void* x, const void* y_or_gx, int dtype,
+                                int B, int C, int h, int w);
+int nmsa_upsample2x_dw3x3_fwd(const void* x, int dtype, const float* weight, const float* bias,
+                              int B, int C, int h, int w, int zeropad, void* y,
+                              nmsa_stream_t stream);
+size_t nmsa_upsample2x_dw3x3_bwd_workspace_bytes(int B, int C, int h, int w);
+int nmsa_upsample2x_dw3x3_bwd(const void* gy, const void* x, int dtype, const float* weight,
+                              int B, int C, int h, int w, int zeropad,
+                              void* gx, float* gweight, float* gbias,
+                              void* workspace, size_t workspace_bytes, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,8 @@ NMSA_SCENE_MAX_CLASSES = 4096
 # include/nmsa.h: bits of nmsa_targets_route
 (NMSA_TG_ROUTE_SCAN, NMSA_TG_ROUTE_FAST_LOADERS, NMSA_TG_ROUTE_PAINT_TILED, NMSA_TG_ROUTE_PAINT_VECTOR,
  NMSA_TG_ROUTE_LUT_LDS, NMSA_TG_ROUTE_SCAN_16) = 1, 2, 4, 8, 16, 32
+# include/nmsa.h: answers of nmsa_upsample2x_dw3x3_route
+NMSA_UP_ROUTE_VECTOR, NMSA_UP_ROUTE_PIXEL = 1, 2
 
 
 class NmsaError(RuntimeError):
@@ -106,6 +108,10 @@ _SIGNATURES = {
     'nmsa_multiscale_nearest': (_i, [_vp, _vp, _i, _i, _vp]),
     'nmsa_batch_augment': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'nmsa_scene_step': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'nmsa_upsample2x_dw3x3_route': (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
+    'nmsa_upsample2x_dw3x3_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'nmsa_upsample2x_dw3x3_bwd_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'nmsa_upsample2x_dw3x3_bwd': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -1150,6 +1150,110 @@ def scene_step(logits: torch.Tensor, labels: Optional[torch.Tensor] = None,
     return out
 
 
+# ----------------------------------------------------------------------------- learned upsampling
+_UP_WORKSPACES: 'collections.OrderedDict[tuple, torch.Tensor]' = __import__('collections').OrderedDict()
+
+
+def _up_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]):
+    _require_on_device(x, 'x')
+    code = L.float_dtype_code(x)                    # TypeError for anything but f32 / bf16 / f16
+    if x.ndim != 4 or x.numel() == 0:
+        raise ValueError(f'x must be a non-empty [B, C, h, w] tensor, got shape {tuple(x.shape)}')
+    C = int(x.shape[1])
+    _require_on_device(weight, 'weight')
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (C, 1, 3, 3):
+        raise TypeError(f'weight must be float32 [{C}, 1, 3, 3], got {weight.dtype} {tuple(weight.shape)}')
+    if bias is not None:
+        _require_on_device(bias, 'bias')
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (C,):
+            raise TypeError(f'bias must be float32 [{C}], got {bias.dtype} {tuple(bias.shape)}')
+    return code
+
+
+def _up_workspace(dev: torch.device, shape: Tuple[int, int, int, int]):
+    """the backward call's partial sums, cached per (device, stream, shape): two streams never share
+    one.  During a graph capture the buffer comes from the graph's memory pool instead."""
+    nbytes = int(L.lib().nmsa_upsample2x_dw3x3_bwd_workspace_bytes(*shape))
+    if torch.cuda.is_current_stream_capturing():
+        # a buffer of the graph's own pool: the capture stream's cache entry would outlive the graph
+        ws = torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
+        return ws, ws.numel() * 4
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, shape)
+    ws = _UP_WORKSPACES.get(key)
+    if ws is None:
+        ws = _UP_WORKSPACES[key] = torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
+        while len(_UP_WORKSPACES) > 16:
+            _UP_WORKSPACES.popitem(last=False)
+    else:
+        _UP_WORKSPACES.move_to_end(key)
+    return ws, ws.numel() * 4
+
+
+def upsample2x_dw3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                     zeropad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's learned x2 upsampling (model/upsampling.py:85-96, modes 'learned-3x3' and, with
+    `zeropad`, 'learned-3x3-zeropad') in one launch (include/nmsa.h nmsa_upsample2x_dw3x3_fwd): nearest
+    x2, replication / zero pad and the depthwise 3x3 convolution.  `x` [B, C, h, w] float32 / bfloat16
+    / float16 on the device (made contiguous when it is not, channels-last included), `weight` float32
+    [C, 1, 3, 3], `bias` float32 [C] or None.  Returns y [B, C, 2h, 2w] in x's dtype, written into `out`
+    when a contiguous tensor of that shape and dtype is given.  No autograd: that is
+    `model.upsampling.LearnedUpsamplingFunction`."""
+    code = _up_check(x, weight, bias)
+    xc, w_, b_ = x.detach().contiguous(), weight.detach().contiguous(), None
+    if bias is not None:
+        b_ = bias.detach().contiguous()
+    B, C, h, w = (int(n) for n in xc.shape)
+    if out is None:
+        y = torch.empty((B, C, 2 * h, 2 * w), dtype=xc.dtype, device=xc.device)
+    else:
+        _require_on_device(out, 'out')
+        if out.dtype != xc.dtype or tuple(out.shape) != (B, C, 2 * h, 2 * w) or not out.is_contiguous():
+            raise TypeError(f'out must be a contiguous {xc.dtype} {(B, C, 2 * h, 2 * w)} tensor')
+        y = out
+    L.check(L.lib().nmsa_upsample2x_dw3x3_fwd(
+        L.ptr(xc), code, L.ptr(w_), L.ptr(b_), B, C, h, w, int(bool(zeropad)), L.ptr(y),
+        L.stream_ptr(xc.device)), 'nmsa_upsample2x_dw3x3_fwd')
+    return y
+
+
+def upsample2x_dw3x3_backward(gy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, zeropad: bool = False,
+                              need_gx: bool = True, need_gweight: bool = True, need_gbias: bool = True):
+    """(gx, gweight, gbias) of `upsample2x_dw3x3` for the upstream gradient `gy` [B, C, 2h, 2w] (x's
+    dtype; made contiguous when it is not), None where not needed (nmsa_upsample2x_dw3x3_bwd).  gx has
+    x's dtype, gweight [C, 1, 3, 3] and gbias [C] are float32.  Deterministic: a fixed order of
+    summation, the same bits on every call."""
+    code = _up_check(x, weight, None)
+    _require_on_device(gy, 'gy')
+    B, C, h, w = (int(n) for n in x.shape)
+    if gy.dtype != x.dtype or tuple(gy.shape) != (B, C, 2 * h, 2 * w):
+        raise TypeError(f'gy must be {x.dtype} {(B, C, 2 * h, 2 * w)}, got {gy.dtype} {tuple(gy.shape)}')
+    g, xc, w_ = gy.detach().contiguous(), x.detach().contiguous(), weight.detach().contiguous()
+    dev = xc.device
+    gx = torch.empty_like(xc) if need_gx else None
+    gw = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=dev) if need_gweight else None
+    gb = torch.empty((C,), dtype=torch.float32, device=dev) if need_gbias else None
+    ws, ws_bytes = _up_workspace(dev, (B, C, h, w)) if (need_gweight or need_gbias) else (None, 0)
+    L.check(L.lib().nmsa_upsample2x_dw3x3_bwd(
+        L.ptr(g), L.ptr(xc), code, L.ptr(w_), B, C, h, w, int(bool(zeropad)),
+        L.ptr(gx), L.ptr(gw), L.ptr(gb), L.ptr(ws), ws_bytes, L.stream_ptr(dev)), 'nmsa_upsample2x_dw3x3_bwd')
+    return gx, gw, gb
+
+
+def upsample2x_dw3x3_route(x: torch.Tensor, other: torch.Tensor) -> int:
+    """The route a call with these tensors takes (`nmsa_upsample2x_dw3x3_route`):
+    L.NMSA_UP_ROUTE_VECTOR or L.NMSA_UP_ROUTE_PIXEL.  `x` [B, C, h, w] is an input-sized tensor of the
+    call, `other` another tensor of it (y, gy or gx); only shapes, the dtype and the addresses are
+    looked at, nothing is launched."""
+    if x.ndim != 4:
+        raise ValueError(f'x must be [B, C, h, w], got shape {tuple(x.shape)}')
+    B, C, h, w = (int(n) for n in x.shape)
+    rc = L.lib().nmsa_upsample2x_dw3x3_route(L.C.c_void_p(x.data_ptr()), L.C.c_void_p(other.data_ptr()),
+                                             L.float_dtype_code(x), B, C, h, w)
+    if rc < 0:
+        L.check(rc, 'nmsa_upsample2x_dw3x3_route')
+    return rc
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""

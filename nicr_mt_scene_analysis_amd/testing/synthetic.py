@@ -743,3 +743,37 @@ def scene_input_digest(inputs) -> str:
     if inputs['weights'] is not None:
         arrays.append(inputs['weights'])
     return input_digest(*arrays)
+
+
+# ----------------------------------------------------------------------------- learned upsampling
+# name: (mode, use_bias, trained, (B, C, h, w), seed) of tests/golden/upsampling.npz; `trained`:
+# random weights (and bias), else the module's initial values
+UPSAMPLING_CASES = {
+    'rep_bias_trained': ('learned-3x3', True, True, (2, 3, 5, 6), 90),
+    'rep_bias_initial': ('learned-3x3', True, False, (1, 4, 3, 7), 91),
+    'rep_nobias_trained': ('learned-3x3', False, True, (2, 2, 9, 4), 92),
+    'rep_nobias_initial': ('learned-3x3', False, False, (1, 3, 1, 5), 93),
+    'zero_bias_trained': ('learned-3x3-zeropad', True, True, (2, 3, 5, 6), 94),
+    'zero_bias_initial': ('learned-3x3-zeropad', True, False, (1, 4, 3, 7), 95),
+    'zero_nobias_trained': ('learned-3x3-zeropad', False, True, (2, 2, 9, 4), 96),
+    'zero_nobias_initial': ('learned-3x3-zeropad', False, False, (1, 3, 1, 5), 97),
+}
+# input of the output-shape record of all four mode names
+UPSAMPLING_SHAPE_INPUT = (1, 2, 3, 5)
+
+
+def make_upsampling_inputs(name: str) -> Dict[str, object]:
+    """The inputs of one case of UPSAMPLING_CASES: 'x' float32 [B,C,h,w], 'gy' float32 [B,C,2h,2w]
+    (the upstream gradient), 'weight' float32 [C,1,3,3] and 'bias' float32 [C] (None where the case
+    keeps the module's initial values / has no bias).  Generator draws and float32 casts only."""
+    _, use_bias, trained, (B, C, h, w), seed = UPSAMPLING_CASES[name]
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((B, C, h, w)).astype(np.float32)
+    gy = rng.standard_normal((B, C, 2 * h, 2 * w)).astype(np.float32)
+    weight = (rng.standard_normal((C, 1, 3, 3)) * 0.25).astype(np.float32) if trained else None
+    bias = rng.standard_normal((C,)).astype(np.float32) if trained and use_bias else None
+    return {'x': x, 'gy': gy, 'weight': weight, 'bias': bias}
+
+
+def upsampling_input_digest(inputs) -> str:
+    return input_digest(*(inputs[k] for k in ('x', 'gy', 'weight', 'bias') if inputs[k] is not None))
