@@ -1117,6 +1117,63 @@ int nmsa_upsample2x_dw3x3_bwd(const void* gy, const void* x, int dtype, const fl
                               void* gx, float* gweight, float* gbias,
                               void* workspace, size_t workspace_bytes, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Swin encoder-decoder fusion (csrc/ln_transpose.hip)
+ *     model/encoder_decoder_fusion.py:123-148, names 'swin-ln-*': LayerNorm over C of the encoder's
+ *     NHWC skip tensor, NHWC -> NCHW, optionally the addition of the decoder features.
+ *
+ *   y[b,c,p]  = ((x[b,p,c] - mean_bp) * rstd_bp) * gamma[c] + beta[c] (+ add[b,c,p])
+ *   gx[b,p,:] = rstd * (a - mean_c(a) - xh * mean_c(a * xh)),   a = gy * gamma, xh = (x - mean) * rstd
+ *   ggamma[c] = sum_bp gy * xh,   gbeta[c] = sum_bp gy
+ *
+ *   x, gx         [B,P,C], P = H*W, C contiguous   NMSA_F32 | NMSA_BF16 | NMSA_F16 (dtype_x)
+ *   y, gy, add    [B,C,P]                          dtype_y = dtype_x or NMSA_F32
+ *   gamma, beta, ggamma, gbeta   f32 [C];   mean, rstd   f32 [B*P]
+ *   Arithmetic: float32 after converting the inputs, no fused multiply-adds.  Every sum over C is a
+ *   tree of depth at most ceil(log2 C) + 2 (a lane's values pairwise, the lanes by halves);
+ *   mean = S / (float)C, var = sum((x - mean)^2) / (float)C (two passes over the row, IEEE division),
+ *   rstd = 1.0f / sqrtf(var + eps), correctly rounded.  A half output is rounded once, to nearest even.
+ *
+ * nmsa_ln_nhwc_nchw_fwd: one launch; x is read twice, the second time right after the first
+ *   (from cache where the tiles in flight fit it), y written once in runs of 32 pixels.  `add` may be NULL.  mean and rstd are written when both are
+ *   non-NULL (training) and must both be NULL otherwise.
+ * nmsa_ln_nhwc_nchw_bwd: gx, ggamma, gbeta of sum(gy * y); each of the three may be NULL (not wanted;
+ *   all NULL: NMSA_OK after the checks, nothing is launched).  One launch over gy and x writes gx
+ *   and one line [2][C] of partial sums per workgroup into `workspace`; a second, small launch adds
+ *   the lines in a fixed order.  No float atomics: two calls on the same inputs give the same bits;
+ *   the grid depends on (B, P, C) and the device geometry only.  `workspace` (16-byte aligned, at
+ *   least nmsa_ln_nhwc_nchw_bwd_workspace_bytes(B, P, C) bytes) is needed only with ggamma or gbeta;
+ *   its contents are scratch.  The gradient of `add` is gy itself.
+ * nmsa_ln_nhwc_nchw_route (host only, nothing is launched, no device is touched): the route a call
+ *   with these two tensors takes.  NMSA_LNT_ROUTE_VECTOR: 16-byte accesses on both sides; taken when
+ *   C % vx == 0 and P % vy == 0 (vx, vy = 4 for a float32, 8 for a half dtype_x / dtype_y) and EVERY
+ *   tensor of the call (fwd: x, y and add; bwd: gy, x and gx) starts on 16 bytes.
+ *   NMSA_LNT_ROUTE_ELEMENT: element-wise accesses, any C <= 2048, any P, any element-aligned
+ *   pointer.  `x` is an [B,P,C] tensor of the call, `y` a [B,C,P] one; a call takes the vector route
+ *   when the answer is NMSA_LNT_ROUTE_VECTOR for every such pair of its tensors.
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a
+ * NULL x / y / gy / gamma / beta, in bwd a NULL mean / rstd, in fwd exactly one of mean / rstd NULL,
+ * dtype_x not one of the three, dtype_y neither dtype_x nor NMSA_F32, B, P or C below 1, eps negative
+ * or not finite (0 is legal), a pointer that is not aligned to its element, a NULL or misaligned
+ * workspace where one is needed.  NMSA_ERR_WORKSPACE: a workspace that is too small.
+ * NMSA_ERR_UNSUPPORTED: C above 2048, B*P*C of 2^31 or more.  No host synchronisation, no
+ * allocation; capturable in a hipGraph as a single chain.
+ * ------------------------------------------------------------------------- */
+#define NMSA_LNT_ROUTE_VECTOR 1
+#define NMSA_LNT_ROUTE_ELEMENT 2
+#define NMSA_LNT_MAX_CHANNELS 2048
+int nmsa_ln_nhwc_nchw_route(const void* x, const void* y, int dtype_x, int dtype_y,
+                            int B, int P, int C);
+int nmsa_ln_nhwc_nchw_fwd(const void* x, int dtype_x, const float* gamma, const float* beta, float eps,
+                          const void* add, int B, int P, int C, void* y, int dtype_y,
+                          float* mean, float* rstd, nmsa_stream_t stream);
+size_t nmsa_ln_nhwc_nchw_bwd_workspace_bytes(int B, int P, int C);
+int nmsa_ln_nhwc_nchw_bwd(const void* gy, int dtype_y, const void* x, int dtype_x, const float* gamma,
+                          const float* mean, const float* rstd, int B, int P, int C,
+                          void* gx, float* ggamma, float* gbeta,
+                          void* workspace, size_t workspace_bytes, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

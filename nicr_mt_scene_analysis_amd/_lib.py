@@ -30,6 +30,9 @@ NMSA_SCENE_MAX_CLASSES = 4096
  NMSA_TG_ROUTE_LUT_LDS, NMSA_TG_ROUTE_SCAN_16) = 1, 2, 4, 8, 16, 32
 # include/nmsa.h: answers of nmsa_upsample2x_dw3x3_route
 NMSA_UP_ROUTE_VECTOR, NMSA_UP_ROUTE_PIXEL = 1, 2
+# include/nmsa.h: answers and channel limit of nmsa_ln_nhwc_nchw_route
+NMSA_LNT_ROUTE_VECTOR, NMSA_LNT_ROUTE_ELEMENT = 1, 2
+NMSA_LNT_MAX_CHANNELS = 2048
 
 
 class NmsaError(RuntimeError):
@@ -112,6 +115,10 @@ _SIGNATURES = {
     'nmsa_upsample2x_dw3x3_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'nmsa_upsample2x_dw3x3_bwd_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'nmsa_upsample2x_dw3x3_bwd': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nmsa_ln_nhwc_nchw_route': (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
+    'nmsa_ln_nhwc_nchw_fwd': (_i, [_vp, _i, _vp, _vp, _f, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    'nmsa_ln_nhwc_nchw_bwd_workspace_bytes': (_sz, [_i, _i, _i]),
+    'nmsa_ln_nhwc_nchw_bwd': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

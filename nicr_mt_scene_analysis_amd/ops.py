@@ -1151,7 +1151,12 @@ def scene_step(logits: torch.Tensor, labels: Optional[torch.Tensor] = None,
 
 
 # ----------------------------------------------------------------------------- learned upsampling
-_UP_WORKSPACES: 'collections.OrderedDict[tuple, torch.Tensor]' = __import__('collections').OrderedDict()
+# partial-sum workspaces of the backward calls (learned upsampling, LayerNorm-transpose), least recently
+# used first out.  One model's set must fit, or every step reallocates: up to five decoders x three
+# skip scales of fusions plus two upsampling stages per head stay well below 64; an entry is at most
+# a few MB (workgroups x 2 x C floats).
+_BWD_WORKSPACES_MAX = 64
+_BWD_WORKSPACES: 'collections.OrderedDict[tuple, torch.Tensor]' = __import__('collections').OrderedDict()
 
 
 def _up_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]):
@@ -1170,23 +1175,27 @@ def _up_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     return code
 
 
-def _up_workspace(dev: torch.device, shape: Tuple[int, int, int, int]):
-    """the backward call's partial sums, cached per (device, stream, shape): two streams never share
-    one.  During a graph capture the buffer comes from the graph's memory pool instead."""
-    nbytes = int(L.lib().nmsa_upsample2x_dw3x3_bwd_workspace_bytes(*shape))
+def _workspace(dev: torch.device, key: tuple, nbytes: int):
+    """a backward call's partial sums, cached per (device, stream, key): two streams never share one.
+    During a graph capture the buffer comes from the graph's memory pool instead.  `key`: the op and
+    its shape; `nbytes`: what the library's size query answers for it."""
     if torch.cuda.is_current_stream_capturing():
         # a buffer of the graph's own pool: the capture stream's cache entry would outlive the graph
         ws = torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
         return ws, ws.numel() * 4
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, shape)
-    ws = _UP_WORKSPACES.get(key)
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream) + key
+    ws = _BWD_WORKSPACES.get(key)
     if ws is None:
-        ws = _UP_WORKSPACES[key] = torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
-        while len(_UP_WORKSPACES) > 16:
-            _UP_WORKSPACES.popitem(last=False)
+        ws = _BWD_WORKSPACES[key] = torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
+        while len(_BWD_WORKSPACES) > _BWD_WORKSPACES_MAX:
+            _BWD_WORKSPACES.popitem(last=False)
     else:
-        _UP_WORKSPACES.move_to_end(key)
+        _BWD_WORKSPACES.move_to_end(key)
     return ws, ws.numel() * 4
+
+
+def _up_workspace(dev: torch.device, shape: Tuple[int, int, int, int]):
+    return _workspace(dev, ('up',) + tuple(shape), int(L.lib().nmsa_upsample2x_dw3x3_bwd_workspace_bytes(*shape)))
 
 
 def upsample2x_dw3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -1251,6 +1260,107 @@ def upsample2x_dw3x3_route(x: torch.Tensor, other: torch.Tensor) -> int:
                                              L.float_dtype_code(x), B, C, h, w)
     if rc < 0:
         L.check(rc, 'nmsa_upsample2x_dw3x3_route')
+    return rc
+
+
+# ------------------------------------------------------- Swin fusion: LayerNorm + NHWC -> NCHW (+ add)
+def _lnt_check(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor]):
+    """-> (dtype code, B, P, C, spatial shape) of an encoder skip tensor [B, H, W, C] or [B, P, C]"""
+    _require_on_device(x, 'x')
+    code = L.float_dtype_code(x)                    # TypeError for anything but f32 / bf16 / f16
+    if x.ndim not in (3, 4) or x.numel() == 0:
+        raise ValueError(f'x must be a non-empty [B, H, W, C] or [B, P, C] tensor, got shape {tuple(x.shape)}')
+    B, C, spatial = int(x.shape[0]), int(x.shape[-1]), tuple(int(n) for n in x.shape[1:-1])
+    for t, name in ((gamma, 'gamma'), (beta, 'beta')):
+        if t is None:
+            continue
+        _require_on_device(t, name)
+        if t.dtype != torch.float32 or tuple(t.shape) != (C,):
+            raise TypeError(f'{name} must be float32 [{C}], got {t.dtype} {tuple(t.shape)}')
+    return code, B, int(np.prod(spatial)), C, spatial
+
+
+def ln_nhwc_to_nchw(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                    add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    out_dtype: Optional[torch.dtype] = None, save_stats: bool = False):
+    """The reference's Swin encoder-decoder fusion (model/encoder_decoder_fusion.py:123-148) in one
+    launch (include/nmsa.h nmsa_ln_nhwc_nchw_fwd): LayerNorm over the last axis of `x` [B, H, W, C]
+    (or [B, P, C]; float32 / bfloat16 / float16 on the device, made contiguous when it is not) with
+    float32 `gamma`, `beta` [C], the result as NCHW [B, C, H, W] ([B, C, P]) in `out_dtype` (x's dtype
+    or float32; default x's), plus `add` (a tensor of the output's shape and dtype) when given.
+    Written into `out` when a contiguous tensor of that shape and dtype is given.  Returns y, or
+    (y, mean, rstd) with `save_stats` (float32 [B*P], what `ln_nhwc_to_nchw_backward` takes).  No
+    autograd: that is `model.encoder_decoder_fusion.SwinFusionFunction`."""
+    code, B, P, C, spatial = _lnt_check(x, gamma, beta)
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (x.dtype, torch.float32):
+        raise TypeError(f'out_dtype must be {x.dtype} or torch.float32, got {out_dtype}')
+    xc, g_, b_ = x.detach().contiguous(), gamma.detach().contiguous(), beta.detach().contiguous()
+    shape = (B, C) + spatial
+    a_ = None
+    if add is not None:
+        _require_on_device(add, 'add')
+        if add.dtype != out_dtype or tuple(add.shape) != shape:
+            raise TypeError(f'add must be {out_dtype} {shape}, got {add.dtype} {tuple(add.shape)}')
+        a_ = add.detach().contiguous()
+    if out is None:
+        y = torch.empty(shape, dtype=out_dtype, device=xc.device)
+    else:
+        _require_on_device(out, 'out')
+        if out.dtype != out_dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise TypeError(f'out must be a contiguous {out_dtype} {shape} tensor')
+        y = out
+    mean = rstd = None
+    if save_stats:
+        mean = torch.empty((B * P,), dtype=torch.float32, device=xc.device)
+        rstd = torch.empty((B * P,), dtype=torch.float32, device=xc.device)
+    L.check(L.lib().nmsa_ln_nhwc_nchw_fwd(
+        L.ptr(xc), code, L.ptr(g_), L.ptr(b_), float(eps), L.ptr(a_), B, P, C, L.ptr(y), L.float_dtype_code(y),
+        L.ptr(mean), L.ptr(rstd), L.stream_ptr(xc.device)), 'nmsa_ln_nhwc_nchw_fwd')
+    return (y, mean, rstd) if save_stats else y
+
+
+def ln_nhwc_to_nchw_backward(gy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, mean: torch.Tensor,
+                             rstd: torch.Tensor, need_gx: bool = True, need_ggamma: bool = True,
+                             need_gbeta: bool = True):
+    """(gx, ggamma, gbeta) of `ln_nhwc_to_nchw` for the upstream gradient `gy` [B, C, H, W] (x's dtype
+    or float32; made contiguous when it is not) and the statistics the forward call saved, None where
+    not needed (nmsa_ln_nhwc_nchw_bwd).  gx has x's shape and dtype, ggamma and gbeta are float32 [C].
+    Deterministic: a fixed order of summation, the same bits on every call."""
+    code, B, P, C, spatial = _lnt_check(x, gamma, None)
+    _require_on_device(gy, 'gy')
+    if gy.dtype not in (x.dtype, torch.float32) or tuple(gy.shape) != (B, C) + spatial:
+        raise TypeError(f'gy must be {x.dtype} or float32 {(B, C) + spatial}, got {gy.dtype} {tuple(gy.shape)}')
+    for t, name in ((mean, 'mean'), (rstd, 'rstd')):
+        _require_on_device(t, name)
+        if t.dtype != torch.float32 or t.numel() != B * P:
+            raise TypeError(f'{name} must be float32 [{B * P}], got {t.dtype} {tuple(t.shape)}')
+    g, xc, g_ = gy.detach().contiguous(), x.detach().contiguous(), gamma.detach().contiguous()
+    m_, r_ = mean.detach().contiguous(), rstd.detach().contiguous()
+    dev = xc.device
+    gx = torch.empty_like(xc) if need_gx else None
+    gg = torch.empty((C,), dtype=torch.float32, device=dev) if need_ggamma else None
+    gb = torch.empty((C,), dtype=torch.float32, device=dev) if need_gbeta else None
+    ws, ws_bytes = (_workspace(dev, ('lnt', B, P, C), int(L.lib().nmsa_ln_nhwc_nchw_bwd_workspace_bytes(B, P, C)))
+                    if (need_ggamma or need_gbeta) else (None, 0))
+    L.check(L.lib().nmsa_ln_nhwc_nchw_bwd(
+        L.ptr(g), L.float_dtype_code(g), L.ptr(xc), code, L.ptr(g_), L.ptr(m_), L.ptr(r_), B, P, C,
+        L.ptr(gx), L.ptr(gg), L.ptr(gb), L.ptr(ws), ws_bytes, L.stream_ptr(dev)), 'nmsa_ln_nhwc_nchw_bwd')
+    return gx, gg, gb
+
+
+def ln_nhwc_to_nchw_route(x: torch.Tensor, y: torch.Tensor) -> int:
+    """The route a call with these tensors takes (`nmsa_ln_nhwc_nchw_route`): L.NMSA_LNT_ROUTE_VECTOR
+    or L.NMSA_LNT_ROUTE_ELEMENT.  `x` [B, H, W, C] / [B, P, C] is an NHWC tensor of the call (x, gx),
+    `y` an NCHW one (y, add, gy); only shapes, dtypes and addresses are looked at, nothing is launched."""
+    if x.ndim not in (3, 4):
+        raise ValueError(f'x must be [B, H, W, C] or [B, P, C], got shape {tuple(x.shape)}')
+    B, C = int(x.shape[0]), int(x.shape[-1])
+    P = int(np.prod([int(n) for n in x.shape[1:-1]]))
+    rc = L.lib().nmsa_ln_nhwc_nchw_route(L.C.c_void_p(x.data_ptr()), L.C.c_void_p(y.data_ptr()),
+                                         L.float_dtype_code(x), L.float_dtype_code(y), B, P, C)
+    if rc < 0:
+        L.check(rc, 'nmsa_ln_nhwc_nchw_route')
     return rc
 
 
