@@ -1174,6 +1174,70 @@ int nmsa_ln_nhwc_nchw_bwd(const void* gy, int dtype_y, const void* x, int dtype_
                           void* gx, float* ggamma, float* gbeta,
                           void* workspace, size_t workspace_bytes, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * context module: pyramid pooling and its concatenation (csrc/context_module.hip)
+ *     model/context_module/ppm.py, appm.py: n adaptive average pools of x, (torch: a 1x1
+ *     ConvNormAct per branch), every branch resized back to H x W and concatenated behind x.
+ *
+ *   x, gx      [B,C,H,W]             NMSA_F32 | NMSA_BF16 | NMSA_F16, contiguous; ONE dtype per call
+ *   pooled_i, gp_i  [B,C,ph_i,pw_i]  i < n_bins <= NMSA_PPM_MAX_BINS, each its own contiguous tensor
+ *   y_i, gy_i  [B,cr_i,ph_i,pw_i]    the branch outputs
+ *   out, g_out [B, C + sum(cr_i), H, W]
+ *   ph, pw, cr and the pointer arrays are HOST arrays of n_bins entries, read during the call and
+ *   carried in the kernel arguments: they may be reused or freed when the call returns.
+ *   Arithmetic: float32 after converting the inputs; a half output is rounded once, to nearest even.
+ *
+ * nmsa_ppm_pool_fwd: ONE launch, x read once.  ATen's windows: rows floor(i*H/ph) .. ceil((i+1)*H/ph)-1,
+ *   columns alike (ph > H included).  pooled = S / float(area), IEEE division, S = the row sums of
+ *   the window added top to bottom, a row sum = its elements added left to right, both from 0.
+ * nmsa_ppm_pool_bwd: ONE launch, gather form: gx[h,w] = the sum over the bins in order, within a
+ *   bin over the cells whose window holds (h,w) in row-major order, of gp_i[cell] / float(area(cell)),
+ *   added from 0.  A NULL gp_i: that branch adds nothing (its gradient is zero).
+ * nmsa_ppm_upcat_fwd: ONE launch.  out[:, 0..C) = x, element for element; behind it branch i,
+ *   y_i resized to H x W with `mode` NMSA_PPM_NEAREST or NMSA_PPM_BILINEAR (align_corners = False)
+ *   in ATen's float arithmetic: scale = float(ph)/float(H); nearest: src = min(int(floorf(dst*scale)),
+ *   ph-1); bilinear: s = max(scale*(dst+0.5f)-0.5f, 0), i0 = min(int(s), ph-1), i1 = min(i0+1, ph-1),
+ *   w1 = s-i0, w0 = 1-w1, value = (a*wx0 + b*wx1)*wy0 + (c*wx0 + d*wx1)*wy1 with one fused
+ *   multiply-add per sum.
+ * nmsa_ppm_upcat_bwd: ONE launch, the transposed resize in gather form:
+ *   gy_i[p,q] = sum_h wy(h,p) * (sum_w wx(w,q) * g_out[C+off_i+c, h, w]) over the output rows h that
+ *   read p (ascending) and the columns w that read q (ascending), fused multiply-adds from 0; wy, wx
+ *   are the weights above (1 for nearest; w0 + w1 where i0 == i1 at the border).  A NULL gy_i: not
+ *   wanted (all NULL: NMSA_OK after the checks, nothing is launched).  The gradient of x through the
+ *   concatenation is the view g_out[:, 0..C) and needs no kernel.
+ * No atomics, no workspace: two calls on the same inputs give the same bits.
+ *
+ * nmsa_ppm_route (host only, nothing is launched, no device is touched): the route pool_fwd and
+ *   upcat_bwd take for this geometry (pool_bwd and upcat_fwd have one route).  NMSA_PPM_ROUTE_LDS: a
+ *   wave stages its plane in LDS and the lanes share the row segments, then the cells; taken when
+ *   H*W <= 2048 and H*pw_i <= 512 for every branch.  NMSA_PPM_ROUTE_GLOBAL: a lane owns a cell and
+ *   walks its window in memory; any size.  Both routes add in the same order and give the same bits.
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a
+ * dtype other than the three, B, C, H or W below 1, n_bins outside 1..NMSA_PPM_MAX_BINS, a NULL
+ * ph / pw / cr / pointer array, a ph_i, pw_i or cr_i below 1, a mode other than the two, a NULL x /
+ * gx / out / g_out / pooled_i / y_i, a pointer that is not aligned to its element.
+ * NMSA_ERR_UNSUPPORTED: H, W, ph_i or pw_i above 32768 (offsets inside a plane are 32-bit, the
+ * plane base is 64-bit), B*C or B*(C + sum cr_i) above 2^31 - 1, 2^31 or more work items.  No host
+ * synchronisation, no allocation; every call is capturable in a hipGraph.
+ * ------------------------------------------------------------------------- */
+#define NMSA_PPM_MAX_BINS 4
+#define NMSA_PPM_NEAREST 0
+#define NMSA_PPM_BILINEAR 1
+#define NMSA_PPM_ROUTE_LDS 1
+#define NMSA_PPM_ROUTE_GLOBAL 2
+int nmsa_ppm_route(int H, int W, int n_bins, const int* ph, const int* pw);
+int nmsa_ppm_pool_fwd(const void* x, int dtype, int B, int C, int H, int W, int n_bins,
+                      const int* ph, const int* pw, void* const* pooled, nmsa_stream_t stream);
+int nmsa_ppm_pool_bwd(const void* const* gp, int dtype, int B, int C, int H, int W, int n_bins,
+                      const int* ph, const int* pw, void* gx, nmsa_stream_t stream);
+int nmsa_ppm_upcat_fwd(const void* x, const void* const* ys, int dtype, int B, int C, int H, int W,
+                       int n_bins, const int* cr, const int* ph, const int* pw, int mode,
+                       void* out, nmsa_stream_t stream);
+int nmsa_ppm_upcat_bwd(const void* g_out, int dtype, int B, int C, int H, int W, int n_bins,
+                       const int* cr, const int* ph, const int* pw, int mode, void* const* gys,
+                       nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,10 @@ NMSA_UP_ROUTE_VECTOR, NMSA_UP_ROUTE_PIXEL = 1, 2
 # include/nmsa.h: answers and channel limit of nmsa_ln_nhwc_nchw_route
 NMSA_LNT_ROUTE_VECTOR, NMSA_LNT_ROUTE_ELEMENT = 1, 2
 NMSA_LNT_MAX_CHANNELS = 2048
+# include/nmsa.h: branch limit, resize modes and route answers of the nmsa_ppm_* entry points
+NMSA_PPM_MAX_BINS = 4
+NMSA_PPM_NEAREST, NMSA_PPM_BILINEAR = 0, 1
+NMSA_PPM_ROUTE_LDS, NMSA_PPM_ROUTE_GLOBAL = 1, 2
 
 
 class NmsaError(RuntimeError):
@@ -119,6 +123,11 @@ _SIGNATURES = {
     'nmsa_ln_nhwc_nchw_fwd': (_i, [_vp, _i, _vp, _vp, _f, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'nmsa_ln_nhwc_nchw_bwd_workspace_bytes': (_sz, [_i, _i, _i]),
     'nmsa_ln_nhwc_nchw_bwd': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nmsa_ppm_route': (_i, [_i, _i, _i, _vp, _vp]),
+    'nmsa_ppm_pool_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'nmsa_ppm_pool_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'nmsa_ppm_upcat_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    'nmsa_ppm_upcat_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

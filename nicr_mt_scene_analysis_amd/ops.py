@@ -1364,6 +1364,179 @@ def ln_nhwc_to_nchw_route(x: torch.Tensor, y: torch.Tensor) -> int:
     return rc
 
 
+# --------------------------------------------- context module: pyramid pooling, upsample + concat
+_PPM_MODES = {'nearest': L.NMSA_PPM_NEAREST, 'bilinear': L.NMSA_PPM_BILINEAR}
+
+
+def _ppm_sizes(sizes) -> Tuple[Tuple[int, int], ...]:
+    """((ph, pw), ...) from a sequence of ints (square) or (ph, pw) pairs"""
+    out = []
+    for s in sizes:
+        ph, pw = (s, s) if isinstance(s, int) else s
+        if int(ph) < 1 or int(pw) < 1:
+            raise ValueError(f'pool sizes must be at least 1, got {s}')
+        out.append((int(ph), int(pw)))
+    if not 1 <= len(out) <= L.NMSA_PPM_MAX_BINS:
+        raise ValueError(f'1..{L.NMSA_PPM_MAX_BINS} pool sizes per call, got {len(out)}')
+    return tuple(out)
+
+
+def _ppm_ints(values):
+    return (L.C.c_int * len(values))(*values)
+
+
+# sizes as given -> (normalised sizes, ph array, pw array): a model asks for the same few tuples in
+# every step, and building them again is a good part of a call's host time at these map sizes
+_PPM_SIZE_ARGS: dict = {}
+
+
+def _ppm_size_args(sizes):
+    key = sizes if isinstance(sizes, tuple) else tuple(tuple(s) if not isinstance(s, int) else s for s in sizes)
+    hit = _PPM_SIZE_ARGS.get(key)
+    if hit is None:
+        sz = _ppm_sizes(key)
+        if len(_PPM_SIZE_ARGS) >= 64:
+            _PPM_SIZE_ARGS.clear()
+        hit = _PPM_SIZE_ARGS[key] = (sz, _ppm_ints([s[0] for s in sz]), _ppm_ints([s[1] for s in sz]))
+    return hit
+
+
+def _ppm_ptrs(tensors):
+    return (L.C.c_void_p * len(tensors))(*(None if t is None else t.data_ptr() for t in tensors))
+
+
+def _ppm_mode(mode) -> int:
+    if mode not in _PPM_MODES:
+        raise ValueError(f"mode must be 'nearest' or 'bilinear', got {mode!r}")
+    return _PPM_MODES[mode]
+
+
+def _ppm_x_check(x: torch.Tensor, name: str = 'x') -> int:
+    _require_on_device(x, name)
+    code = L.float_dtype_code(x)                    # TypeError for anything but f32 / bf16 / f16
+    if x.ndim != 4 or x.numel() == 0:
+        raise TypeError(f'{name} must be a non-empty [B, C, H, W] tensor, got shape {tuple(x.shape)}')
+    return code
+
+
+def ppm_pool(x: torch.Tensor, sizes) -> Tuple[torch.Tensor, ...]:
+    """All adaptive average pools of the context module in one launch (include/nmsa.h
+    nmsa_ppm_pool_fwd): `x` [B, C, H, W] float32 / bfloat16 / float16 on the device (made contiguous
+    when it is not, channels-last included), `sizes` 1..4 ints or (ph, pw) pairs.  Returns one
+    contiguous [B, C, ph, pw] tensor per size in x's dtype: `F.adaptive_avg_pool2d(x, size)` with
+    float32 sums.  No autograd: that is `model.context_module.PyramidPoolFunction`."""
+    code = _ppm_x_check(x)
+    sz, phs, pws = _ppm_size_args(sizes)
+    xc = x.detach().contiguous()
+    B, C, H, W = xc.shape
+    outs = tuple(torch.empty((B, C, ph, pw), dtype=xc.dtype, device=xc.device) for ph, pw in sz)
+    L.check(L.lib().nmsa_ppm_pool_fwd(
+        L.ptr(xc), code, B, C, H, W, len(sz), phs, pws, _ppm_ptrs(outs), L.stream_ptr(xc.device)),
+        'nmsa_ppm_pool_fwd')
+    return outs
+
+
+def ppm_pool_backward(gps, x_shape, sizes) -> torch.Tensor:
+    """gx [B, C, H, W] of `ppm_pool` for the gradients `gps` of its outputs (one per size, all of one
+    dtype, [B, C, ph, pw], made contiguous when they are not; None: that output was not used) in one
+    launch (nmsa_ppm_pool_bwd).  Deterministic: a gather in a fixed order, the same bits on every call."""
+    sz, phs, pws = _ppm_size_args(sizes)
+    B, C, H, W = (int(n) for n in x_shape)
+    gps = tuple(gps)
+    given = [g for g in gps if g is not None]
+    if len(gps) != len(sz) or not given:
+        raise TypeError(f'one gradient (or None) per size and at least one tensor, got {len(gps)} for {len(sz)} sizes')
+    code = _ppm_x_check(given[0], 'gps')
+    gc = []
+    for g, (ph, pw) in zip(gps, sz):
+        if g is None:
+            gc.append(None)
+            continue
+        _require_on_device(g, 'gps')
+        if g.dtype != given[0].dtype or tuple(g.shape) != (B, C, ph, pw):
+            raise TypeError(f'gps must be {given[0].dtype} {(B, C, ph, pw)}, got {g.dtype} {tuple(g.shape)}')
+        gc.append(g.detach().contiguous())
+    dev = given[0].device
+    gx = torch.empty((B, C, H, W), dtype=given[0].dtype, device=dev)
+    L.check(L.lib().nmsa_ppm_pool_bwd(
+        _ppm_ptrs(gc), code, B, C, H, W, len(sz), phs, pws, L.ptr(gx), L.stream_ptr(dev)), 'nmsa_ppm_pool_bwd')
+    return gx
+
+
+def ppm_upsample_concat(x: torch.Tensor, ys, mode: str = 'bilinear',
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`torch.cat([x] + [F.interpolate(y, (H, W), mode) for y in ys], 1)` in one launch
+    (nmsa_ppm_upcat_fwd): `x` [B, C, H, W] float32 / bfloat16 / float16 on the device, `ys` 1..4
+    branch outputs [B, Cr_i, ph_i, pw_i] of x's dtype (all made contiguous when they are not), `mode`
+    'nearest' or 'bilinear' (align_corners=False).  Returns [B, C + sum Cr_i, H, W], written into `out`
+    when a contiguous tensor of that shape and dtype is given.  No autograd: that is
+    `model.context_module.UpsampleConcatFunction`."""
+    code = _ppm_x_check(x)
+    m = _ppm_mode(mode)
+    xc = x.detach().contiguous()
+    B, C, H, W = (int(n) for n in xc.shape)
+    ys = tuple(ys)
+    if not 1 <= len(ys) <= L.NMSA_PPM_MAX_BINS:
+        raise ValueError(f'1..{L.NMSA_PPM_MAX_BINS} branches per call, got {len(ys)}')
+    yc = []
+    for y in ys:
+        _require_on_device(y, 'ys')
+        if y.dtype != xc.dtype or y.ndim != 4 or int(y.shape[0]) != B or y.numel() == 0:
+            raise TypeError(f'ys must be non-empty {xc.dtype} [{B}, Cr, ph, pw] tensors, got {y.dtype} {tuple(y.shape)}')
+        yc.append(y.detach().contiguous())
+    shape = (B, C + sum(int(y.shape[1]) for y in yc), H, W)
+    if out is None:
+        o = torch.empty(shape, dtype=xc.dtype, device=xc.device)
+    else:
+        _require_on_device(out, 'out')
+        if out.dtype != xc.dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise TypeError(f'out must be a contiguous {xc.dtype} {shape} tensor')
+        o = out
+    L.check(L.lib().nmsa_ppm_upcat_fwd(
+        L.ptr(xc), _ppm_ptrs(yc), code, B, C, H, W, len(yc), _ppm_ints([int(y.shape[1]) for y in yc]),
+        _ppm_ints([int(y.shape[2]) for y in yc]), _ppm_ints([int(y.shape[3]) for y in yc]), m, L.ptr(o),
+        L.stream_ptr(xc.device)), 'nmsa_ppm_upcat_fwd')
+    return o
+
+
+def ppm_upsample_concat_backward(g_out: torch.Tensor, n_channels_x: int, branch_shapes, mode: str = 'bilinear',
+                                 need=None) -> Tuple[Optional[torch.Tensor], ...]:
+    """The gradients of the branch outputs of `ppm_upsample_concat` for the upstream gradient `g_out`
+    [B, C + sum Cr_i, H, W] (made contiguous when it is not) in one launch (nmsa_ppm_upcat_bwd).
+    `branch_shapes`: the shapes [B, Cr_i, ph_i, pw_i] of the branches; `need`: one bool per branch
+    (default all), None is returned for the others.  The gradient of x is the view
+    `g_out[:, :n_channels_x]`: no kernel.  Deterministic: a gather in a fixed order."""
+    code = _ppm_x_check(g_out, 'g_out')
+    m = _ppm_mode(mode)
+    shapes = [tuple(int(n) for n in s) for s in branch_shapes]
+    if not 1 <= len(shapes) <= L.NMSA_PPM_MAX_BINS:
+        raise ValueError(f'1..{L.NMSA_PPM_MAX_BINS} branches per call, got {len(shapes)}')
+    need = [True] * len(shapes) if need is None else [bool(n) for n in need]
+    B, Ct, H, W = (int(n) for n in g_out.shape)
+    C = int(n_channels_x)
+    if (len(need) != len(shapes) or any(len(s) != 4 or s[0] != B or min(s) < 1 for s in shapes)
+            or C < 1 or C + sum(s[1] for s in shapes) != Ct):
+        raise TypeError(f'g_out {tuple(g_out.shape)} does not match {C} channels of x and the branches {shapes}')
+    g = g_out.detach().contiguous()
+    gys = tuple(torch.empty(s, dtype=g.dtype, device=g.device) if n else None for s, n in zip(shapes, need))
+    L.check(L.lib().nmsa_ppm_upcat_bwd(
+        L.ptr(g), code, B, C, H, W, len(shapes), _ppm_ints([s[1] for s in shapes]),
+        _ppm_ints([s[2] for s in shapes]), _ppm_ints([s[3] for s in shapes]), m, _ppm_ptrs(gys),
+        L.stream_ptr(g.device)), 'nmsa_ppm_upcat_bwd')
+    return gys
+
+
+def ppm_route(hw: Tuple[int, int], sizes) -> int:
+    """The route `ppm_pool` and `ppm_upsample_concat_backward` take for a map of `hw` = (H, W) and
+    these pool sizes (`nmsa_ppm_route`): L.NMSA_PPM_ROUTE_LDS or L.NMSA_PPM_ROUTE_GLOBAL.  Host only,
+    nothing is launched."""
+    sz, phs, pws = _ppm_size_args(sizes)
+    rc = L.lib().nmsa_ppm_route(int(hw[0]), int(hw[1]), len(sz), phs, pws)
+    if rc < 0:
+        L.check(rc, 'nmsa_ppm_route')
+    return rc
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""

@@ -9,3 +9,8 @@ DecoderRawOutputType = Tuple[Any, Any]          # (outputs, side_outputs)
 DecoderPostprocessedOutputType = Dict[str, Any]
 PostprocessingOutputType = DecoderPostprocessedOutputType
 TensorOrTuple = Union[Tensor, Tuple[Tensor, ...]]
+
+# context module (reference types.py:23-26)
+ContextModuleInputType = Tensor
+ContextModuleContextFeaturesType = Union[Tuple[Tensor, ...], Tuple[()]]
+ContextModuleOutputType = Tuple[Tensor, ContextModuleContextFeaturesType]
