@@ -1238,6 +1238,62 @@ int nmsa_ppm_upcat_bwd(const void* g_out, int dtype, int B, int C, int H, int W,
                        const int* cr, const int* ph, const int* pw, int mode, void* const* gys,
                        nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * MLP decoders: every branch resized into the concatenation (csrc/mlp_decoder.hip)
+ *     model/decoder/mlp_base.py: the embedded main map (1/32) and skips (1/16, 1/8, 1/4) resized to
+ *     the 1/4-resolution grid and concatenated in front of the 1x1 `fuse` convolution (torch: one
+ *     interpolate per branch and a cat).
+ *
+ *   out[b, off_i + c, Y, X] = resize(y_i[b, c], H x W),   off_i = c_0 + ... + c_(i-1)
+ *   y_i, gy_i  [B, c_i, H >> s_i, W >> s_i]   i < n <= NMSA_MLPDEC_MAX_BRANCHES, s_i in 0..4, each its
+ *                                             own contiguous tensor
+ *   out, g_out [B, sum(c_i), H, W]            NMSA_F32 | NMSA_BF16 | NMSA_F16, ONE dtype per call
+ *   c, s and the pointer arrays are HOST arrays of n entries, read during the call and carried in the
+ *   kernel arguments: they may be reused or freed when the call returns.  H and W are multiples of
+ *   1 << s_i for every branch.
+ *   Arithmetic: exactly that of nmsa_ppm_upcat_fwd / _bwd above (ATen's float index arithmetic with
+ *   scale = float(h)/float(H), the blend (a*wx0 + b*wx1)*wy0 + (c*wx0 + d*wx1)*wy1 with one fused
+ *   multiply-add per sum, backward in gather form with fused multiply-adds from 0, left to right,
+ *   then top to bottom, weights w0 + w1 where i0 == i1); float32 inside, a half output is rounded
+ *   once.  `mode` is NMSA_MLPDEC_NEAREST or NMSA_MLPDEC_BILINEAR (align_corners = False).
+ *   A branch with s_i == 0 is copied element for element.  Stated deviation: ATen's scale-1 bilinear
+ *   turns -0 into +0 and an inf next to a zero weight into NaN; the copy keeps both.
+ *
+ * nmsa_mlpdec_upcat_fwd: ONE launch, every output element written once.
+ * nmsa_mlpdec_upcat_bwd: ONE launch; a lane owns a source pixel and gathers its footprint (at most
+ *   2f x 2f output pixels bilinear, f x f nearest, f = 1 << s_i).  A NULL gy_i: not wanted (all NULL:
+ *   NMSA_OK after the checks, nothing is launched).  The gradient of a branch with s_i == 0 is the view
+ *   g_out[:, off_i .. off_i + c_i) and needs no kernel: pass NULL for it (a pointer gets the same
+ *   values through the gather, one pixel per lane; a -0 arrives as +0).
+ * No atomics, no workspace: every call and every route gives the same bits.
+ *
+ * nmsa_mlpdec_route (host only, nothing is launched, no device is touched): the route upcat_fwd takes
+ *   with these tensors (upcat_bwd has one route).  NMSA_MLPDEC_ROUTE_VECTOR: a lane produces 4
+ *   (float32) or 8 (half) consecutive pixels of a row and stores 16 bytes; taken when W is a multiple
+ *   of that count and EVERY tensor of the call (out and every y_i) starts on 16 bytes.
+ *   NMSA_MLPDEC_ROUTE_ELEMENT: one pixel per lane, any width, any element-aligned pointer.  Both
+ *   routes give the same bits.
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a
+ * dtype other than the three, a mode other than the two, B, H, W or a c_i below 1, n outside
+ * 1..NMSA_MLPDEC_MAX_BRANCHES, an s_i outside 0..4, H or W not a multiple of 1 << s_i, a NULL c / s /
+ * pointer array, a NULL out / g_out / y_i, a pointer that is not aligned to its element.
+ * NMSA_ERR_UNSUPPORTED (after those): H or W above 32768 (offsets inside a plane are 32-bit, the plane
+ * base is 64-bit), B * sum(c_i) above 2^31 - 1, 2^31 or more work items.  No host synchronisation, no
+ * allocation; both calls are capturable in a hipGraph.
+ * ------------------------------------------------------------------------- */
+#define NMSA_MLPDEC_MAX_BRANCHES 4
+#define NMSA_MLPDEC_NEAREST 0
+#define NMSA_MLPDEC_BILINEAR 1
+#define NMSA_MLPDEC_ROUTE_VECTOR 1
+#define NMSA_MLPDEC_ROUTE_ELEMENT 2
+int nmsa_mlpdec_route(const void* const* ys, const void* out, int dtype, int H, int W, int n,
+                      const int* s);
+int nmsa_mlpdec_upcat_fwd(const void* const* ys, int dtype, int B, int H, int W, int n, const int* c,
+                          const int* s, int mode, void* out, nmsa_stream_t stream);
+int nmsa_mlpdec_upcat_bwd(const void* g_out, int dtype, int B, int H, int W, int n, const int* c,
+                          const int* s, int mode, void* const* gys, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,10 @@ NMSA_LNT_MAX_CHANNELS = 2048
 NMSA_PPM_MAX_BINS = 4
 NMSA_PPM_NEAREST, NMSA_PPM_BILINEAR = 0, 1
 NMSA_PPM_ROUTE_LDS, NMSA_PPM_ROUTE_GLOBAL = 1, 2
+# include/nmsa.h: branch limit, resize modes and route answers of the nmsa_mlpdec_* entry points
+NMSA_MLPDEC_MAX_BRANCHES = 4
+NMSA_MLPDEC_NEAREST, NMSA_MLPDEC_BILINEAR = 0, 1
+NMSA_MLPDEC_ROUTE_VECTOR, NMSA_MLPDEC_ROUTE_ELEMENT = 1, 2
 
 
 class NmsaError(RuntimeError):
@@ -128,6 +132,9 @@ _SIGNATURES = {
     'nmsa_ppm_pool_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'nmsa_ppm_upcat_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     'nmsa_ppm_upcat_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    'nmsa_mlpdec_route': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'nmsa_mlpdec_upcat_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    'nmsa_mlpdec_upcat_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

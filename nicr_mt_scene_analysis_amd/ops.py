@@ -1537,6 +1537,117 @@ def ppm_route(hw: Tuple[int, int], sizes) -> int:
     return rc
 
 
+# ------------------------------------------------ MLP decoders: all branches into the concatenation
+_MLPDEC_MODES = {'nearest': L.NMSA_MLPDEC_NEAREST, 'bilinear': L.NMSA_MLPDEC_BILINEAR}
+_MLPDEC_MAX_SHIFT = 4
+
+
+def _mlpdec_mode(mode) -> int:
+    if mode not in _MLPDEC_MODES:
+        raise ValueError(f"mode must be 'nearest' or 'bilinear', got {mode!r}")
+    return _MLPDEC_MODES[mode]
+
+
+def _mlpdec_shifts(shapes, size=None) -> Tuple[int, int, Tuple[int, ...]]:
+    """(H, W, (s_0, ...)) from the branch shapes [B, c_i, h_i, w_i]: H x W is `size`, by default the
+    largest map, and every branch must reach it by one power-of-two factor 1 << s_i up to 16, the same
+    along H and W.  ValueError for anything else: another factor, factors that differ between H and W, maps that do
+    not meet at one output size, no branch or more than four."""
+    shapes = [tuple(int(n) for n in s) for s in shapes]
+    if not 1 <= len(shapes) <= L.NMSA_MLPDEC_MAX_BRANCHES:
+        raise ValueError(f'1..{L.NMSA_MLPDEC_MAX_BRANCHES} branches per call, got {len(shapes)}')
+    if any(len(s) != 4 or min(s) < 1 for s in shapes):
+        raise ValueError(f'branches must be non-empty [B, c, h, w] maps, got {shapes}')
+    H, W = (max(s[2] for s in shapes), max(s[3] for s in shapes)) if size is None else (int(size[0]), int(size[1]))
+    shifts = []
+    for s in shapes:
+        if H % s[2] or W % s[3]:
+            raise ValueError(f'a {s[2]}x{s[3]} map does not reach {H}x{W} by a whole factor')
+        fh, fw = H // s[2], W // s[3]
+        if fh != fw:
+            raise ValueError(f'a {s[2]}x{s[3]} map reaches {H}x{W} by {fh} along H and {fw} along W')
+        if fh & (fh - 1) or fh > 1 << _MLPDEC_MAX_SHIFT:
+            raise ValueError(f'factor {fh} is not a power of two up to {1 << _MLPDEC_MAX_SHIFT}')
+        shifts.append(fh.bit_length() - 1)
+    return H, W, tuple(shifts)
+
+
+def mlpdec_upsample_concat(ys, mode: str = 'bilinear', size=None) -> torch.Tensor:
+    """`torch.cat([F.interpolate(y, (H, W), mode) for y in ys], 1)` in one launch
+    (nmsa_mlpdec_upcat_fwd): `ys` 1..4 maps [B, c_i, H >> s_i, W >> s_i] of one dtype (float32 /
+    bfloat16 / float16) on the device, made contiguous when they are not; H x W is `size`, by default
+    the largest of them, and every factor a power of two up to 16 (`_mlpdec_shifts`).  `mode`
+    'nearest' or 'bilinear' (align_corners=False); a branch that is already H x W is copied.  Returns
+    [B, sum c_i, H, W].  No autograd: that is `model.decoder.MlpUpsampleConcatFunction`."""
+    ys = tuple(ys)
+    m = _mlpdec_mode(mode)
+    for y in ys:
+        _require_on_device(y, 'ys')
+    H, W, shifts = _mlpdec_shifts([tuple(y.shape) for y in ys], size)
+    code = _ppm_x_check(ys[0], 'ys')
+    B = int(ys[0].shape[0])
+    yc = []
+    for y in ys:
+        if y.dtype != ys[0].dtype or int(y.shape[0]) != B or y.device != ys[0].device:
+            raise TypeError(f'ys must be {ys[0].dtype} [{B}, c, h, w] tensors on one device, '
+                            f'got {y.dtype} {tuple(y.shape)}')
+        yc.append(y.detach().contiguous())
+    cs = [int(y.shape[1]) for y in yc]
+    out = torch.empty((B, sum(cs), H, W), dtype=yc[0].dtype, device=yc[0].device)
+    L.check(L.lib().nmsa_mlpdec_upcat_fwd(
+        _ppm_ptrs(yc), code, B, H, W, len(yc), _ppm_ints(cs), _ppm_ints(shifts), m, L.ptr(out),
+        L.stream_ptr(out.device)), 'nmsa_mlpdec_upcat_fwd')
+    return out
+
+
+def mlpdec_upsample_concat_backward(g_out: torch.Tensor, branch_shapes, mode: str = 'bilinear',
+                                    need=None) -> Tuple[Optional[torch.Tensor], ...]:
+    """The gradients of the branches of `mlpdec_upsample_concat` for the upstream gradient `g_out`
+    [B, sum c_i, H, W] (made contiguous when it is not) in one launch (nmsa_mlpdec_upcat_bwd).
+    `branch_shapes`: the shapes [B, c_i, h_i, w_i]; `need`: one bool per branch (default all), None is
+    returned for the others.  The gradient of a branch that is already H x W is the view
+    `g_out[:, off_i:off_i + c_i]`: no kernel.  Deterministic: a gather in a fixed order."""
+    code = _ppm_x_check(g_out, 'g_out')
+    m = _mlpdec_mode(mode)
+    shapes = [tuple(int(n) for n in s) for s in branch_shapes]
+    H, W, shifts = _mlpdec_shifts(shapes, (g_out.shape[2], g_out.shape[3]) if g_out.ndim == 4 else None)
+    need = [True] * len(shapes) if need is None else [bool(n) for n in need]
+    B, Ct = int(g_out.shape[0]), int(g_out.shape[1])
+    if (len(need) != len(shapes) or any(s[0] != B for s in shapes) or sum(s[1] for s in shapes) != Ct
+            or (int(g_out.shape[2]), int(g_out.shape[3])) != (H, W)):
+        raise TypeError(f'g_out {tuple(g_out.shape)} does not match the branches {shapes}')
+    g = g_out.detach().contiguous()
+    gys, off = [], 0
+    for s, sh, n in zip(shapes, shifts, need):
+        if not n:
+            gys.append(None)
+        elif sh == 0:
+            gys.append(g[:, off:off + s[1]])
+        else:
+            gys.append(torch.empty(s, dtype=g.dtype, device=g.device))
+        off += s[1]
+    asked = [t if t is not None and sh else None for t, sh in zip(gys, shifts)]
+    if any(t is not None for t in asked):
+        L.check(L.lib().nmsa_mlpdec_upcat_bwd(
+            L.ptr(g), code, B, H, W, len(shapes), _ppm_ints([s[1] for s in shapes]), _ppm_ints(shifts), m,
+            _ppm_ptrs(asked), L.stream_ptr(g.device)), 'nmsa_mlpdec_upcat_bwd')
+    return tuple(gys)
+
+
+def mlpdec_route(ys, out: torch.Tensor) -> int:
+    """The route `mlpdec_upsample_concat` takes with the branch maps `ys` and the output tensor `out`
+    (`nmsa_mlpdec_route`): L.NMSA_MLPDEC_ROUTE_VECTOR (16 bytes per lane: W a multiple of 4 float32 /
+    8 half pixels and every tensor on 16 bytes) or L.NMSA_MLPDEC_ROUTE_ELEMENT.  Host only, nothing is
+    launched; the backward has one route."""
+    ys = tuple(ys)
+    H, W, shifts = _mlpdec_shifts([tuple(y.shape) for y in ys], (out.shape[2], out.shape[3]))
+    rc = L.lib().nmsa_mlpdec_route(_ppm_ptrs(ys), L.ptr(out), L.float_dtype_code(out), H, W, len(ys),
+                                   _ppm_ints(shifts))
+    if rc < 0:
+        L.check(rc, 'nmsa_mlpdec_route')
+    return rc
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""

@@ -14,3 +14,10 @@ TensorOrTuple = Union[Tensor, Tuple[Tensor, ...]]
 ContextModuleInputType = Tensor
 ContextModuleContextFeaturesType = Union[Tuple[Tensor, ...], Tuple[()]]
 ContextModuleOutputType = Tuple[Tensor, ContextModuleContextFeaturesType]
+
+# encoder and decoder (reference types.py:17-21, 29, 49)
+EncoderForwardType = Dict[str, Tensor]              # modality: features
+EncoderSkipType = EncoderForwardType
+EncoderSkipsType = Dict[str, EncoderSkipType]       # downsampling: skip features
+DecoderInputType = ContextModuleOutputType
+DecoderOutputType = Union[DecoderRawOutputType, DecoderPostprocessedOutputType]
