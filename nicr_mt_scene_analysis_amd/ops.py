@@ -1178,19 +1178,20 @@ def _up_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
 def _workspace(dev: torch.device, key: tuple, nbytes: int):
     """a backward call's partial sums, cached per (device, stream, key): two streams never share one.
     During a graph capture the buffer comes from the graph's memory pool instead.  `key`: the op and
-    its shape; `nbytes`: what the library's size query answers for it."""
+    its shape; `nbytes`: what the library's size query answers for it NOW: a query that follows the
+    launch grid (LayerNorm-transpose: workgroups x 2 x C floats) answers more for the same shape once
+    the library sees more compute units, so a cached buffer that is too small is replaced."""
     if torch.cuda.is_current_stream_capturing():
         # a buffer of the graph's own pool: the capture stream's cache entry would outlive the graph
         ws = torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
         return ws, ws.numel() * 4
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream) + key
     ws = _BWD_WORKSPACES.get(key)
-    if ws is None:
+    if ws is None or ws.numel() * 4 < nbytes:
         ws = _BWD_WORKSPACES[key] = torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
         while len(_BWD_WORKSPACES) > _BWD_WORKSPACES_MAX:
             _BWD_WORKSPACES.popitem(last=False)
-    else:
-        _BWD_WORKSPACES.move_to_end(key)
+    _BWD_WORKSPACES.move_to_end(key)
     return ws, ws.numel() * 4
 
 

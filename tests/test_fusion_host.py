@@ -180,3 +180,18 @@ def test_torch_float32_meets_the_bounds_and_the_one_pass_variance_does_not(C):
             ref, bd = R.reference64(x, gamma, beta, eps, None, gy), R.bounds(x, gamma, beta, eps, None, gy)
             worst = max(worst, R.worst_ratio({'y': y1, 'gx': gx1}[key], ref[key], bd[key]))
         assert worst > factor, (kind, key, worst)
+
+
+@pytest.mark.parametrize('cus', (1, 3, 256))
+def test_backward_workspace_follows_the_assumed_compute_units(monkeypatch, cus):
+    """the partial sums of nmsa_ln_nhwc_nchw_bwd are one line [2][C] of floats per workgroup, and the
+    grid is min(tiles, 4 workgroups per compute unit) (csrc/ln_transpose.hip LNT_BWD_BLOCKS_PER_CU):
+    the size query follows NMSA_ASSUME_CUS, on both sides of the cap and at it.  No device needed."""
+    monkeypatch.setenv('NMSA_ASSUME_CUS', str(cus))
+    assert L.device_geometry()[0] == cus
+    cap, query = 4 * cus, L.lib().nmsa_ln_nhwc_nchw_bwd_workspace_bytes
+    for C in (64, 160):
+        for tiles in (max(1, cap - 1), cap, cap + 1, 3 * cap + 1):
+            for B, P in ((1, 32 * tiles), (1, 32 * tiles - 31)) + (((2, 16 * tiles),) if tiles % 2 == 0 else ()):
+                assert B * -(-P // 32) == tiles
+                assert query(B, P, C) == min(tiles, cap) * 2 * C * 4, (cus, C, B, P)
