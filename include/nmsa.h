@@ -1294,6 +1294,95 @@ int nmsa_mlpdec_upcat_fwd(const void* const* ys, int dtype, int B, int H, int W,
 int nmsa_mlpdec_upcat_bwd(const void* g_out, int dtype, int B, int H, int W, int n, const int* c,
                           const int* s, int mode, void* const* gys, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * encoder RGB-D fusion: SE-weighted add (csrc/encoder_fusion.hip)
+ *     model/encoder_fusion.py, names 'se-add*': per modality m (0 = rgb, 1 = depth) a squeeze-and-
+ *     excitation weighting of the feature map, then the sum of the two weighted maps.
+ *
+ *   s_m[b,c]  = mean over the plane of x_m[b,c]
+ *   z1_m = W1_m s_m + b1_m,   h_m = act(z1_m),   w_m = sigmoid(W2_m h_m + b2_m)       R = C / 16 (floor)
+ *   y[b,c,p]  = x_rgb[b,c,p] * w_rgb[b,c] + x_depth[b,c,p] * w_depth[b,c]
+ *   gw_m[b,c] = sum over the plane of gy * x_m
+ *   gz2_m = gw_m * w_m * (1 - w_m),  gh_m = W2_m^T gz2_m,  gz1_m = gh_m * act'(z1_m),  gs_m = W1_m^T gz1_m
+ *   gx_m[b,c,p] = gy[b,c,p] * w_m[b,c] + gs_m[b,c] / (H*W)
+ *
+ *   x_rgb, x_depth, y, gy, gx_rgb, gx_depth  [B,C,H,W] contiguous, NMSA_F32 | NMSA_BF16 | NMSA_F16,
+ *                                            ONE dtype per call
+ *   s, w, gw, gz2, gs  f32 [2,B,C];   z1, gz1, h  f32 [2,B,R];   the modality is the outer index
+ *   W1 f32 [R,C], b1 f32 [R], W2 f32 [C,R], b2 f32 [C] per modality.  `params` is a HOST array of 8
+ *   pointers (W1, b1, W2, b2 of rgb, then of depth), `weights` one of 4 (W1, W2 of rgb, then of
+ *   depth); both are read during the call and may be reused when it returns.
+ *   `act` is NMSA_SEFUSE_ACT_RELU (act' = 0 at z1 <= 0, ATen's threshold backward) or
+ *   NMSA_SEFUSE_ACT_SILU (z sig(z); act' = sig(z) * (1 + z * (1 - sig(z)))).
+ *
+ *   Arithmetic: float32 after converting the inputs; a half output is rounded once, to nearest even.
+ *   Plane sums (squeeze, weight_grad): the plane is cut into chunks of V = 4 (float32) / 8 (half)
+ *   consecutive elements; with T = 64 lanes (NMSA_SEFUSE_ROUTE_WAVE, H*W <= NMSA_SEFUSE_WAVE_PLANE_MAX)
+ *   or T = 1024 lanes (NMSA_SEFUSE_ROUTE_BLOCK) lane t owns chunks t, t + T, ... and keeps V partial
+ *   sums, one per position in the chunk, each added in ascending chunk order from 0 (weight_grad: fused
+ *   multiply-adds of gy and x).  A lane's partials are added pairwise ((a0 + a1) + (a2 + a3)) + ...,
+ *   the 64 lanes of a wave by halves (l += l + 32, 16, 8, 4, 2, 1), the 16 waves of the BLOCK route in
+ *   wave order.  s = S / float(H*W), IEEE division.  The order depends on H*W and the dtype only.
+ *   excite: z1[r] = (sum_c W1[r,c] s[c]) + b1[r], lane l of a wave adding c = l, l + 64, ... as fused
+ *   multiply-adds from 0, the lanes by halves; w[c] = 1 / (1 + expf(-((sum_r W2[c,r] h[r]) + b2[c]))),
+ *   fused multiply-adds from 0 in ascending r, IEEE division.  excite_bwd: gz2 = (gw * w) * (1 - w);
+ *   gh like z1 (over c), gs like the sum of w (over r).
+ *   scale_add: the two products and their sum, each rounded to float32.  apply_bwd: the product, the
+ *   IEEE quotient gs / float(H*W) and their sum, each rounded to float32.
+ *
+ * nmsa_sefuse_squeeze: ONE launch, s of both modalities.
+ * nmsa_sefuse_excite: ONE launch, one workgroup per (modality, image); writes w and, when z1 is not
+ *   NULL (training), z1.
+ * nmsa_sefuse_scale_add: ONE launch.
+ * nmsa_sefuse_weight_grad: ONE launch, both modalities from one read of gy.  A NULL x_m: that half of
+ *   gw is not wanted and not written (both NULL: NMSA_OK after the checks, nothing is launched).
+ * nmsa_sefuse_excite_bwd: ONE launch; writes gz2, gz1, gs and h (= act(z1), recomputed) of the
+ *   modalities whose W1 and W2 are both given; both NULL: that modality is not wanted and its halves
+ *   are not written (all four NULL: NMSA_OK after the checks, nothing is launched).
+ * nmsa_sefuse_apply_bwd: ONE launch.  A NULL gx_m: not wanted (both NULL: NMSA_OK after the checks).
+ * No atomics, no workspace, no hand-off between workgroups: two calls on the same inputs give the same
+ * bits.  The four map kernels launch at most 8 workgroups of 256 lanes (BLOCK route: 2 of 1024) per
+ * compute unit of nmsa_device_geometry and LOOP over the rest of their items.
+ *
+ * nmsa_sefuse_route (host only, nothing is launched, no device is touched): the routes a map call
+ *   with the tensors t0, t1, t2 (t1, t2 may be NULL: not part of the call) takes, two bits or-ed.
+ *   NMSA_SEFUSE_ROUTE_VECTOR: 16-byte accesses; taken when H*W is a multiple of V and EVERY tensor of
+ *   the call starts on 16 bytes.  NMSA_SEFUSE_ROUTE_ELEMENT: element-wise accesses, any H*W, any
+ *   element-aligned pointer.  Both give the same bits (in the plane sums a lane reads the same chunks
+ *   either way).  NMSA_SEFUSE_ROUTE_WAVE / NMSA_SEFUSE_ROUTE_BLOCK: how squeeze and weight_grad cut a
+ *   plane (see above; scale_add and apply_bwd have no such split).
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a dtype
+ * other than the three, an activation other than the two, B, H or W below 1, C below 16, a NULL
+ * pointer where none is allowed (every tensor except x_m of weight_grad, gx_m of apply_bwd, z1 of
+ * excite and whole modalities of `weights`), only one of W1 / W2 of a modality in `weights`, a pointer
+ * that is not aligned to its element.  NMSA_ERR_UNSUPPORTED (after those): B*C*H*W of 2^31 or more
+ * (map calls), C above NMSA_SEFUSE_MAX_CHANNELS (excite, excite_bwd).  No host synchronisation, no
+ * allocation; every call is capturable in a hipGraph as a single chain.
+ * ------------------------------------------------------------------------- */
+#define NMSA_SEFUSE_ACT_RELU 0
+#define NMSA_SEFUSE_ACT_SILU 1
+#define NMSA_SEFUSE_ROUTE_VECTOR 1
+#define NMSA_SEFUSE_ROUTE_ELEMENT 2
+#define NMSA_SEFUSE_ROUTE_WAVE 4
+#define NMSA_SEFUSE_ROUTE_BLOCK 8
+#define NMSA_SEFUSE_WAVE_PLANE_MAX 2048
+#define NMSA_SEFUSE_MAX_CHANNELS 2048
+int nmsa_sefuse_route(const void* t0, const void* t1, const void* t2, int dtype, int H, int W);
+int nmsa_sefuse_squeeze(const void* x_rgb, const void* x_depth, int dtype, int B, int C, int H, int W,
+                        float* s, nmsa_stream_t stream);
+int nmsa_sefuse_excite(const float* s, const float* const* params, int act, int B, int C, float* w,
+                       float* z1, nmsa_stream_t stream);
+int nmsa_sefuse_scale_add(const void* x_rgb, const void* x_depth, int dtype, const float* w, int B,
+                          int C, int H, int W, void* y, nmsa_stream_t stream);
+int nmsa_sefuse_weight_grad(const void* gy, const void* x_rgb, const void* x_depth, int dtype, int B,
+                            int C, int H, int W, float* gw, nmsa_stream_t stream);
+int nmsa_sefuse_excite_bwd(const float* gw, const float* w, const float* z1,
+                           const float* const* weights, int act, int B, int C, float* gz2, float* gz1,
+                           float* gs, float* h, nmsa_stream_t stream);
+int nmsa_sefuse_apply_bwd(const void* gy, int dtype, const float* w, const float* gs, int B, int C,
+                          int H, int W, void* gx_rgb, void* gx_depth, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

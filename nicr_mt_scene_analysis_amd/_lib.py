@@ -41,6 +41,12 @@ NMSA_PPM_ROUTE_LDS, NMSA_PPM_ROUTE_GLOBAL = 1, 2
 NMSA_MLPDEC_MAX_BRANCHES = 4
 NMSA_MLPDEC_NEAREST, NMSA_MLPDEC_BILINEAR = 0, 1
 NMSA_MLPDEC_ROUTE_VECTOR, NMSA_MLPDEC_ROUTE_ELEMENT = 1, 2
+# include/nmsa.h: activation codes, route bits and limits of the nmsa_sefuse_* entry points
+NMSA_SEFUSE_ACT_RELU, NMSA_SEFUSE_ACT_SILU = 0, 1
+NMSA_SEFUSE_ROUTE_VECTOR, NMSA_SEFUSE_ROUTE_ELEMENT = 1, 2
+NMSA_SEFUSE_ROUTE_WAVE, NMSA_SEFUSE_ROUTE_BLOCK = 4, 8
+NMSA_SEFUSE_WAVE_PLANE_MAX = 2048
+NMSA_SEFUSE_MAX_CHANNELS = 2048
 
 
 class NmsaError(RuntimeError):
@@ -135,6 +141,13 @@ _SIGNATURES = {
     'nmsa_mlpdec_route': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'nmsa_mlpdec_upcat_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     'nmsa_mlpdec_upcat_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    'nmsa_sefuse_route': (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    'nmsa_sefuse_squeeze': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'nmsa_sefuse_excite': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'nmsa_sefuse_scale_add': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'nmsa_sefuse_weight_grad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'nmsa_sefuse_excite_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'nmsa_sefuse_apply_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -1,9 +1,13 @@
-"""Building blocks of the model (reference model/utils.py); only what the encoder-decoder fusion
-needs: `ConvNormAct`, a convolution (1x1 by default) followed by a normalization and an activation,
-with the reference's sub-module names `conv`, `norm`, `act`.  Plain torch."""
+"""Building blocks of the model (reference model/utils.py), plain torch:
+`ConvNormAct`, a convolution (1x1 by default) followed by a normalization and an activation, with the
+reference's sub-module names `conv`, `norm`, `act` (the encoder-decoder fusion's channel adapter);
+`SqueezeAndExcitation`, the channel weighting of the encoder RGB-D fusion, with the reference's
+sub-module layout `layers.{0..3}`.  `model.encoder_fusion` reads its parameters for the fused HIP path
+and calls it as it is everywhere else."""
 from typing import Optional, Type
 
-from torch import nn
+import torch.nn.functional as F
+from torch import Tensor, nn
 
 from .activation import get_activation_class
 from .normalization import get_normalization_class
@@ -22,3 +26,20 @@ class ConvNormAct(nn.Sequential):
             self.add_module('norm', normalization(n_channels_out))
         if activation is not None:
             self.add_module('act', activation())
+
+
+class SqueezeAndExcitation(nn.Module):
+    def __init__(self, n_channels: int, reduction: int = 16,
+                 activation: Type[nn.Module] = get_activation_class()) -> None:
+        super().__init__()
+        n_channels_red = n_channels // reduction
+        assert n_channels_red > 0
+        self.layers = nn.Sequential(
+            nn.Conv2d(n_channels, n_channels_red, kernel_size=1),
+            activation(),
+            nn.Conv2d(n_channels_red, n_channels, kernel_size=1),
+            nn.Sigmoid(),
+        )
+
+    def forward(self, x: Tensor) -> Tensor:
+        return x * self.layers(F.adaptive_avg_pool2d(x, 1))

@@ -1649,6 +1649,197 @@ def mlpdec_route(ys, out: torch.Tensor) -> int:
     return rc
 
 
+# ------------------------------------------------------- encoder RGB-D fusion: SE-weighted add
+_SEFUSE_ACTS = {'relu': L.NMSA_SEFUSE_ACT_RELU, 'silu': L.NMSA_SEFUSE_ACT_SILU}
+
+
+def _sefuse_act(act) -> int:
+    if act not in _SEFUSE_ACTS:
+        raise ValueError(f"act must be 'relu' or 'silu', got {act!r}")
+    return _SEFUSE_ACTS[act]
+
+
+def _sefuse_maps(first: torch.Tensor, others, names) -> Tuple[int, Tuple[int, int, int, int], list]:
+    """dtype code, (B, C, H, W) and the detached, contiguous maps of a call: `first` sets device, dtype
+    and shape, every tensor of `others` (None allowed) must match it"""
+    code = _ppm_x_check(first, names[0])
+    shape = tuple(int(n) for n in first.shape)
+    if shape[1] < 16:
+        raise ValueError(f'the SE weighting needs at least 16 channels, got {shape[1]}')
+    maps = [first.detach().contiguous()]
+    for t, name in zip(others, names[1:]):
+        if t is None:
+            maps.append(None)
+            continue
+        _require_on_device(t, name)
+        if t.dtype != first.dtype or tuple(t.shape) != shape or t.device != first.device:
+            raise TypeError(f'{name} must be {first.dtype} {shape} on {first.device}, got {t.dtype} '
+                            f'{tuple(t.shape)} on {t.device}')
+        maps.append(t.detach().contiguous())
+    return code, shape, maps
+
+
+def _sefuse_vec(t: torch.Tensor, shape, name: str) -> torch.Tensor:
+    _require_on_device(t, name)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise TypeError(f'{name} must be float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
+    return t.detach().contiguous()
+
+
+def _sefuse_out(out, shape, dtype, device, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _require_on_device(out, name)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise TypeError(f'{name} must be a contiguous {dtype} {tuple(shape)} tensor')
+    return out
+
+
+def _sefuse_params(params, C: int, device, n_each: int):
+    """the float32 parameter tensors of one call as a pointer array: per modality W1 [R, C], b1 [R],
+    W2 [C, R], b2 [C] (`n_each` = 4) or W1, W2 (`n_each` = 2); 1x1 convolution weights [.., .., 1, 1]
+    are taken as they are.  A modality given as None is passed as NULL pointers."""
+    R = C // 16
+    shapes = ((R, C), (R,), (C, R), (C,)) if n_each == 4 else ((R, C), (C, R))
+    keep, flat = [], []
+    for m, group in enumerate(params):
+        if group is None:
+            flat.extend([None] * n_each)
+            continue
+        if len(group) != n_each:
+            raise TypeError(f'{n_each} parameter tensors per modality, got {len(group)}')
+        for t, shape in zip(group, shapes):
+            _require_on_device(t, 'params')
+            if t.dtype != torch.float32 or t.numel() != int(np.prod(shape)) or tuple(t.shape[:len(shape)]) != shape:
+                raise TypeError(f'parameter of modality {m} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}')
+            t = t.detach().contiguous()
+            keep.append(t)
+            flat.append(t)
+    return keep, _ppm_ptrs(flat)
+
+
+def sefuse_squeeze(x_rgb: torch.Tensor, x_depth: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """s float32 [2, B, C]: the plane means of `x_rgb` (s[0]) and `x_depth` (s[1]), both [B, C, H, W] of
+    one dtype (float32 / bfloat16 / float16) on the device, in one launch (include/nmsa.h
+    nmsa_sefuse_squeeze): float32 sums in a fixed order, no atomics."""
+    code, (B, C, H, W), (xr, xd) = _sefuse_maps(x_rgb, (x_depth,), ('x_rgb', 'x_depth'))
+    s = _sefuse_out(out, (2, B, C), torch.float32, xr.device, 'out')
+    L.check(L.lib().nmsa_sefuse_squeeze(L.ptr(xr), L.ptr(xd), code, B, C, H, W, L.ptr(s), L.stream_ptr(xr.device)),
+            'nmsa_sefuse_squeeze')
+    return s
+
+
+def sefuse_excite(s: torch.Tensor, params_rgb, params_depth, act: str = 'relu', save_z1: bool = False):
+    """w float32 [2, B, C] = sigmoid(W2 act(W1 s + b1) + b2) per modality from the squeeze `s` [2, B, C]
+    in one launch (nmsa_sefuse_excite).  `params_*`: (W1 [C//16, C], b1, W2 [C, C//16], b2) float32 on the
+    device (the 1x1 convolution weights as they are); `act` 'relu' or 'silu'.  With `save_z1` returns
+    (w, z1), z1 float32 [2, B, C//16] the hidden pre-activation `sefuse_excite_backward` takes."""
+    a = _sefuse_act(act)
+    _require_on_device(s, 's')
+    if s.ndim != 3 or s.shape[0] != 2 or s.dtype != torch.float32 or s.numel() == 0:
+        raise TypeError(f's must be a non-empty float32 [2, B, C] tensor, got {s.dtype} {tuple(s.shape)}')
+    B, C = int(s.shape[1]), int(s.shape[2])
+    if C < 16:
+        raise ValueError(f'the SE weighting needs at least 16 channels, got {C}')
+    sc = s.detach().contiguous()
+    keep, ptrs = _sefuse_params((params_rgb, params_depth), C, sc.device, 4)
+    if len(keep) != 8:
+        raise TypeError('the parameters of both modalities are needed')
+    w = torch.empty((2, B, C), dtype=torch.float32, device=sc.device)
+    z1 = torch.empty((2, B, C // 16), dtype=torch.float32, device=sc.device) if save_z1 else None
+    L.check(L.lib().nmsa_sefuse_excite(L.ptr(sc), ptrs, a, B, C, L.ptr(w), L.ptr(z1), L.stream_ptr(sc.device)),
+            'nmsa_sefuse_excite')
+    return (w, z1) if save_z1 else w
+
+
+def sefuse_scale_add(x_rgb: torch.Tensor, x_depth: torch.Tensor, w: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x_rgb * w[0][:, :, None, None] + x_depth * w[1][:, :, None, None] in one launch
+    (nmsa_sefuse_scale_add): float32 arithmetic, one rounding to the maps' dtype.  `w` float32
+    [2, B, C]; written into `out` when a contiguous tensor of the maps' shape and dtype is given."""
+    code, (B, C, H, W), (xr, xd) = _sefuse_maps(x_rgb, (x_depth,), ('x_rgb', 'x_depth'))
+    wc = _sefuse_vec(w, (2, B, C), 'w')
+    y = _sefuse_out(out, (B, C, H, W), xr.dtype, xr.device, 'out')
+    L.check(L.lib().nmsa_sefuse_scale_add(L.ptr(xr), L.ptr(xd), code, L.ptr(wc), B, C, H, W, L.ptr(y),
+                                          L.stream_ptr(xr.device)), 'nmsa_sefuse_scale_add')
+    return y
+
+
+def sefuse_weight_grad(gy: torch.Tensor, x_rgb: Optional[torch.Tensor], x_depth: Optional[torch.Tensor],
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gw float32 [2, B, C]: the plane sums of gy * x_rgb (gw[0]) and gy * x_depth (gw[1]) from one read of
+    `gy` in one launch (nmsa_sefuse_weight_grad); fixed order, no atomics.  A map given as None is not
+    read and its half of gw is zero (left as it is in a given `out`)."""
+    code, (B, C, H, W), (g, xr, xd) = _sefuse_maps(gy, (x_rgb, x_depth), ('gy', 'x_rgb', 'x_depth'))
+    if out is not None:
+        gw = _sefuse_out(out, (2, B, C), torch.float32, g.device, 'out')
+    elif xr is None or xd is None:
+        gw = torch.zeros((2, B, C), dtype=torch.float32, device=g.device)
+    else:
+        gw = torch.empty((2, B, C), dtype=torch.float32, device=g.device)
+    L.check(L.lib().nmsa_sefuse_weight_grad(L.ptr(g), L.ptr(xr), L.ptr(xd), code, B, C, H, W, L.ptr(gw),
+                                            L.stream_ptr(g.device)), 'nmsa_sefuse_weight_grad')
+    return gw
+
+
+def sefuse_excite_backward(gw: torch.Tensor, w: torch.Tensor, z1: torch.Tensor, weights_rgb, weights_depth,
+                           act: str = 'relu'):
+    """(gz2 [2, B, C], gz1 [2, B, C//16], gs [2, B, C], h [2, B, C//16]) float32 of `sefuse_excite` for the
+    weight gradient `gw` in one launch (nmsa_sefuse_excite_bwd): gz2 = gw w (1 - w), gz1 = (W2^T gz2)
+    act'(z1), gs = W1^T gz1, h = act(z1).  `weights_*`: (W1, W2) of the modality, or None: that
+    modality is not wanted and its halves are zero."""
+    a = _sefuse_act(act)
+    _require_on_device(gw, 'gw')
+    if gw.ndim != 3 or gw.shape[0] != 2 or gw.numel() == 0:
+        raise TypeError(f'gw must be a non-empty float32 [2, B, C] tensor, got {tuple(gw.shape)}')
+    B, C = int(gw.shape[1]), int(gw.shape[2])
+    if C < 16:
+        raise ValueError(f'the SE weighting needs at least 16 channels, got {C}')
+    R = C // 16
+    g = _sefuse_vec(gw, (2, B, C), 'gw')
+    wc = _sefuse_vec(w, (2, B, C), 'w')
+    z = _sefuse_vec(z1, (2, B, R), 'z1')
+    keep, ptrs = _sefuse_params((weights_rgb, weights_depth), C, g.device, 2)
+    make = torch.empty if len(keep) == 4 else torch.zeros
+    gz2, gs = (make((2, B, C), dtype=torch.float32, device=g.device) for _ in range(2))
+    gz1, h = (make((2, B, R), dtype=torch.float32, device=g.device) for _ in range(2))
+    L.check(L.lib().nmsa_sefuse_excite_bwd(L.ptr(g), L.ptr(wc), L.ptr(z), ptrs, a, B, C, L.ptr(gz2), L.ptr(gz1),
+                                           L.ptr(gs), L.ptr(h), L.stream_ptr(g.device)), 'nmsa_sefuse_excite_bwd')
+    return gz2, gz1, gs, h
+
+
+def sefuse_apply_backward(gy: torch.Tensor, w: torch.Tensor, gs: torch.Tensor, need_rgb: bool = True,
+                          need_depth: bool = True, out_rgb: Optional[torch.Tensor] = None,
+                          out_depth: Optional[torch.Tensor] = None):
+    """(gx_rgb, gx_depth), gx_m = gy * w[m] + gs[m] / (H * W), in gy's dtype in one launch
+    (nmsa_sefuse_apply_bwd); None for a modality that is not needed."""
+    code, (B, C, H, W), (g,) = _sefuse_maps(gy, (), ('gy',))
+    wc = _sefuse_vec(w, (2, B, C), 'w')
+    gsc = _sefuse_vec(gs, (2, B, C), 'gs')
+    gxr = _sefuse_out(out_rgb, (B, C, H, W), g.dtype, g.device, 'out_rgb') if need_rgb else None
+    gxd = _sefuse_out(out_depth, (B, C, H, W), g.dtype, g.device, 'out_depth') if need_depth else None
+    if need_rgb or need_depth:
+        L.check(L.lib().nmsa_sefuse_apply_bwd(L.ptr(g), code, L.ptr(wc), L.ptr(gsc), B, C, H, W, L.ptr(gxr),
+                                              L.ptr(gxd), L.stream_ptr(g.device)), 'nmsa_sefuse_apply_bwd')
+    return gxr, gxd
+
+
+def sefuse_route(*tensors: torch.Tensor) -> int:
+    """The routes a map call of the SE-weighted add takes with these 1..3 [B, C, H, W] tensors
+    (`nmsa_sefuse_route`): L.NMSA_SEFUSE_ROUTE_VECTOR or _ELEMENT (16-byte accesses: H*W a multiple of
+    4 float32 / 8 half elements and every tensor on 16 bytes), or-ed with L.NMSA_SEFUSE_ROUTE_WAVE or
+    _BLOCK (how the squeeze and the weight gradient cut a plane: one wave up to
+    L.NMSA_SEFUSE_WAVE_PLANE_MAX elements, one workgroup above).  Host only, nothing is launched."""
+    if not 1 <= len(tensors) <= 3 or any(t.ndim != 4 for t in tensors):
+        raise ValueError('1..3 [B, C, H, W] tensors')
+    ptrs = [L.C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (3 - len(tensors))
+    rc = L.lib().nmsa_sefuse_route(*ptrs, L.float_dtype_code(tensors[0]), int(tensors[0].shape[2]),
+                                   int(tensors[0].shape[3]))
+    if rc < 0:
+        L.check(rc, 'nmsa_sefuse_route')
+    return rc
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""

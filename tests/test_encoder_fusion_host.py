@@ -1,0 +1,221 @@
+"""CPU tier of the encoder RGB-D fusion (model/encoder_fusion.py): exports, the seven names, state
+dicts, the torch composition against the recorded reference module, object identities, the 'nhwc'
+layout, and the error bounds of testing/encoder_fusion_ref.py held against torch's own float32 and
+against three defective restatements BEFORE any kernel is held to them.  No test needs a device."""
+import os
+
+import pytest
+import torch
+from torch import nn
+
+from nicr_mt_scene_analysis_amd import model
+from nicr_mt_scene_analysis_amd.model.activation import get_activation_class
+from nicr_mt_scene_analysis_amd.model.utils import SqueezeAndExcitation
+from nicr_mt_scene_analysis_amd.testing import encoder_fusion_cases as EC
+from nicr_mt_scene_analysis_amd.testing import encoder_fusion_ref as R
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'encoder_fusion.npz')
+CHECKED = ('s', 'z1', 'h', 'w', 'y', 'gw', 'gz2', 'gz1', 'gs', 'gx_rgb', 'gx_depth') + R.PARAM_GRADS
+
+
+@pytest.fixture(scope='module')
+def golden():
+    return EC.GoldenFile(GOLDEN)
+
+
+def build(name, C, act, layout='nchw'):
+    return model.get_encoder_fusion_class(name)(n_channels_in=C, input_memory_layout=layout,
+                                                activation=get_activation_class(act))
+
+
+def run_record(module, rec):
+    """outputs and gradients of `module` on the record's inputs and upstream gradients"""
+    x = {m: rec[f'x_{m}'].clone().requires_grad_(True) for m in ('rgb', 'depth')}
+    y = module(x)
+    ((y['rgb'] * rec['gy_rgb']).sum() + (y['depth'] * rec['gy_depth']).sum()).backward()
+    return x, y
+
+
+# ------------------------------------------------------------------------------ interface
+def test_exports():
+    for name in ('KNOWN_ENCODER_FUSIONS', 'EncoderRGBDFusionWeightedAdd', 'EncoderFusionType',
+                 'get_encoder_fusion_class', 'SqueezeAndExcitation'):
+        assert hasattr(model, name), name
+    assert model.EncoderFusionType is model.EncoderRGBDFusionWeightedAdd
+    assert model.SqueezeAndExcitation is SqueezeAndExcitation
+    assert tuple(model.KNOWN_ENCODER_FUSIONS) == EC.NAMES
+
+
+@pytest.mark.parametrize('name', EC.NAMES)
+def test_names_map_to_the_reference_settings(name):
+    for spelled in (name, name.upper()):
+        m = model.get_encoder_fusion_class(spelled)(n_channels_in=32, input_memory_layout='nchw')
+        assert isinstance(m, model.EncoderRGBDFusionWeightedAdd)
+        assert (m._use_se_weighting, tuple(m._destinations)) == EC.EXPECTED[name]
+        assert hasattr(m, 'weighting_rgb') == hasattr(m, 'weighting_depth') == EC.EXPECTED[name][0]
+
+
+def test_default_and_unknown_names():
+    m = model.get_encoder_fusion_class()(n_channels_in=32, input_memory_layout='nchw')
+    assert (m._use_se_weighting, tuple(m._destinations)) == EC.EXPECTED['add-uni-rgb']
+    for bad in ('se', 'add-rgb', 'se-add-uni', ''):
+        with pytest.raises(ValueError):
+            model.get_encoder_fusion_class(bad)
+
+
+@pytest.mark.parametrize('C', (16, 32, 48, 100))
+def test_state_dict_keys_and_shapes(C):
+    R_ = C // 16
+    state = build('se-add', C, 'relu').state_dict()
+    expected = {}
+    for m in ('rgb', 'depth'):
+        expected.update({f'weighting_{m}.layers.0.weight': (R_, C, 1, 1), f'weighting_{m}.layers.0.bias': (R_,),
+                         f'weighting_{m}.layers.2.weight': (C, R_, 1, 1), f'weighting_{m}.layers.2.bias': (C,)})
+    assert {k: tuple(v.shape) for k, v in state.items()} == expected
+    assert build('add', C, 'relu').state_dict() == {}
+
+
+def test_squeeze_and_excitation_layout_and_assert():
+    se = SqueezeAndExcitation(64, activation=get_activation_class('silu'))
+    assert isinstance(se.layers[0], nn.Conv2d) and isinstance(se.layers[1], nn.SiLU)
+    assert isinstance(se.layers[2], nn.Conv2d) and isinstance(se.layers[3], nn.Sigmoid)
+    assert se.layers[0].weight.shape == (4, 64, 1, 1) and se.layers[2].weight.shape == (64, 4, 1, 1)
+    assert SqueezeAndExcitation(64, reduction=4).layers[0].out_channels == 16
+    assert isinstance(SqueezeAndExcitation(32).layers[1], nn.ReLU)
+    with pytest.raises(AssertionError):
+        SqueezeAndExcitation(8)
+    with pytest.raises(AssertionError):
+        build('se-add', 8, 'relu')
+    build('add', 8, 'relu')                         # no weighting, no limit
+
+
+# ------------------------------------------------------------------------------ the fixture
+def test_the_fixture_is_data_of_the_stated_layout(golden):
+    assert sorted(golden.index) == sorted(EC.record_name(*r) for r in EC.golden_records())
+    assert os.path.getsize(GOLDEN) <= os.path.getsize(os.path.join(os.path.dirname(GOLDEN), 'mlp_decoder.npz'))
+    for name, act, k in EC.golden_records():
+        rec = golden.record(EC.record_name(name, act, k))
+        inp = EC.golden_inputs(k)
+        for field in EC.GOLDEN_FIELDS:
+            assert rec[field].dtype == torch.float32 and tuple(rec[field].shape) == EC.GOLDEN_SHAPES[k], field
+        for field, t in inp.items():
+            assert torch.equal(rec[field], t), (name, field)
+        assert bool(golden.state_dict(rec)) == EC.EXPECTED[name][0]
+
+
+@pytest.mark.parametrize('name,act,k', EC.golden_records())
+def test_cpu_composition_reproduces_the_recorded_reference(golden, name, act, k):
+    rec = golden.record(EC.record_name(name, act, k))
+    module = build(name, EC.GOLDEN_SHAPES[k][1], act)
+    module.load_state_dict(golden.state_dict(rec), strict=True)
+    x, y = run_record(module, rec)
+    se = EC.EXPECTED[name][0]
+
+    def same(a, b):
+        # the same ATen ops as the reference module: float32 resolution; no arithmetic beyond one add
+        # without the weighting: exact
+        return torch.allclose(a, b, rtol=1e-6, atol=1e-7) if se else torch.equal(a, b)
+    for m in ('rgb', 'depth'):
+        assert same(y[m].detach(), rec[f'y_{m}']), (m, 'y')
+        assert same(x[m].grad, rec[f'gx_{m}']), (m, 'gx')
+    for key, p in module.named_parameters():
+        assert torch.allclose(p.grad, rec[f'grad/{key}'], rtol=1e-5, atol=1e-7), key
+
+
+@pytest.mark.parametrize('name', EC.NAMES)
+@pytest.mark.parametrize('layout', ('nchw', 'nhwc'))
+def test_object_identities(name, layout):
+    module = build(name, 32, 'relu', layout)
+    shape = (2, 32, 4, 5) if layout == 'nchw' else (2, 4, 5, 32)
+    x = {'rgb': torch.randn(shape), 'depth': torch.randn(shape)}
+    y = module(x)
+    dest = EC.EXPECTED[name][1]
+    for m in ('rgb', 'depth'):
+        assert (y[m] is x[m]) == (m not in dest), m
+    assert (y['rgb'] is y['depth']) == (len(dest) == 2)
+    assert set(y) == {'rgb', 'depth'}
+
+
+@pytest.mark.parametrize('name', ('se-add', 'se-add-uni-depth', 'add'))
+@pytest.mark.parametrize('act', EC.ACTS)
+def test_nhwc_composition_equals_nchw_on_permuted_inputs(name, act):
+    a, b = build(name, 48, act, 'nchw'), build(name, 48, act, 'nhwc')
+    b.load_state_dict(a.state_dict())
+    x = {'rgb': torch.randn(2, 48, 5, 6), 'depth': torch.randn(2, 48, 5, 6)}
+    ya = a(x)
+    yb = b({m: t.permute(0, 2, 3, 1) for m, t in x.items()})
+    for m in ('rgb', 'depth'):
+        assert yb[m].shape == (2, 5, 6, 48)
+        assert torch.equal(yb[m].permute(0, 3, 1, 2), ya[m]), m
+    with pytest.raises(ValueError):
+        build('se-add', 48, act, 'nwhc')({m: t for m, t in x.items()})
+
+
+# ------------------------------------------------------------------------------ the bounds
+def torch_float32(x_rgb, x_depth, params, act, gy):
+    """every checked quantity from torch's own float32 evaluation of `torch_formulation` (autograd)"""
+    xr, xd = x_rgb.clone().requires_grad_(True), x_depth.clone().requires_grad_(True)
+    ps = tuple(tuple(p.clone().requires_grad_(True) for p in group) for group in params)
+    y = R.torch_formulation(xr, xd, ps, act)
+    y.backward(gy)
+    out = {'y': y.detach(), 'gx_rgb': xr.grad, 'gx_depth': xd.grad}
+    for i, key in enumerate(R.PARAM_GRADS):
+        out[key] = torch.stack((ps[0][i].grad, ps[1][i].grad))
+    return out
+
+
+def ratios(got, ref, bnd):
+    return {key: R.worst_ratio(got[key], ref[key], bnd[key]) for key in got}
+
+
+@pytest.fixture(scope='module')
+def bound_cases():
+    """(C, hw, act) -> (inputs, params, reference64, bounds), computed once"""
+    out = {}
+    for i, (C, hw) in enumerate(EC.SHAPES):
+        for act in EC.ACTS:
+            x_rgb, x_depth, gy = R.make_inputs(EC.B, C, hw, 300 + i)
+            params = R.make_params(C, 400 + i)
+            out[(C, hw, act)] = ((x_rgb, x_depth, gy), params, R.reference64(x_rgb, x_depth, params, act, gy),
+                                 R.bounds(x_rgb, x_depth, params, act, gy))
+    return out
+
+
+def test_reference64_and_bounds_have_every_quantity(bound_cases):
+    (x_rgb, _, _), _, ref, bnd = bound_cases[(48, (3, 5), 'silu')]
+    for key in CHECKED:
+        assert ref[key].dtype == torch.float64 and ref[key].shape == bnd[key].shape, key
+        assert bool((bnd[key] >= 0).all()) and bool(torch.isfinite(bnd[key]).all()), key
+    assert ref['gW1'].shape == (2, 3, 48) and ref['gW2'].shape == (2, 48, 3) and ref['y'].shape == x_rgb.shape
+
+
+@pytest.mark.parametrize('C,hw', EC.SHAPES)
+@pytest.mark.parametrize('act', EC.ACTS)
+def test_torch_float32_lies_within_the_bounds(bound_cases, C, hw, act):
+    (x_rgb, x_depth, gy), params, ref, bnd = bound_cases[(C, hw, act)]
+    worst = ratios(torch_float32(x_rgb, x_depth, params, act, gy), ref, bnd)
+    print(f'C {C} {hw} {act}: ' + ' '.join(f'{k} {v:.3f}' for k, v in worst.items()))
+    assert max(worst.values()) <= 1.0, worst
+
+
+@pytest.mark.parametrize('C,hw', [s for s in EC.SHAPES if s[1] != (1, 1)])
+@pytest.mark.parametrize('act', EC.ACTS)
+def test_defective_restatements_lie_outside_the_bounds(bound_cases, C, hw, act):
+    (x_rgb, x_depth, gy), params, ref, bnd = bound_cases[(C, hw, act)]
+    # what each defect must move out of its bound: the mean by H*W - 1 moves s (by s / (H*W), which the
+    # order-free bound of a large plane's sum, growing with H*W, leaves outside only for s itself), w
+    # instead of w (1 - w) moves gz2 and the gradients behind it; the dropped gs / (H*W) term moves the gradient
+    # of a map wherever gs is not zero (under ReLU every hidden unit of a modality may be inactive: at
+    # least one modality is held to it)
+    for defect, keys, every in (('mean', ('s',), True), ('no_gs', ('gx_rgb', 'gx_depth'), False),
+                                ('sig_grad', ('gz2', 'gb2'), True)):
+        bad = R.reference64(x_rgb, x_depth, params, act, gy, defect=defect)
+        moved = {key: R.worst_ratio(bad[key], ref[key], bnd[key]) for key in keys}
+        assert (min if every else max)(moved.values()) > 1.0, (defect, moved)
+
+
+def test_sigmoid_roundoff_is_measured_not_assumed():
+    z = torch.linspace(-20, 20, 4001, dtype=torch.float64)
+    K = R.sigmoid_roundoff(z)
+    assert 3.0 <= K < 64.0, K
+    assert R.sigmoid_roundoff(torch.zeros(4, dtype=torch.float64)) == 3.0
