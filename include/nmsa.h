@@ -1383,6 +1383,93 @@ int nmsa_sefuse_excite_bwd(const float* gw, const float* w, const float* z1,
 int nmsa_sefuse_apply_bwd(const void* gy, int dtype, const float* w, const float* gs, int B, int C,
                           int H, int W, void* gx_rgb, void* gx_depth, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * residual blocks: the fused batch-norm tail (csrc/block_tail.hip)
+ *     model/block.py, every norm-to-activation segment of BasicBlock, Bottleneck and NonBottleneck1D:
+ *     batch normalization, the Dropout2d scale, the residual add and the activation.
+ *
+ *   training: mean_c = sum(x) / M,  var_c = sum((x - mean_c)^2) / M,  M = B*H*W      eval: running_mean, running_var
+ *   invstd = 1 / sqrt(var + eps)    xh = (x - mean) * invstd    u = xh * gamma + beta
+ *   v = u * s[b,c]  (s NULL: u)     z = v + id  (id NULL: v)    y = act(z)
+ *   gz = gy * act'(z)    gid = gz    gu = gz * s    dbeta = sum(gu)    dgamma = sum(gu * xh)
+ *   training: gx = (gamma * invstd) * ((gu - dbeta / M) - xh * (dgamma / M))     eval: gx = (gamma * invstd) * gu
+ *
+ *   x, identity, y, gy, gx, gid  [B,C,H,W] contiguous, NMSA_F32 | NMSA_BF16 | NMSA_F16, ONE dtype per call
+ *   scale  [B,C] of the same dtype (the Dropout2d scale, 0 or 1 / (1 - p))
+ *   gamma, beta, running_mean, running_var, save_mean, save_invstd, mean, invstd, dgamma, dbeta  f32 [C]
+ *   part  f32 [C, U, 2], U = B * ceil(H*W / NMSA_BNTAIL_SEGMENT): the caller's workspace of
+ *         nmsa_bntail_workspace_bytes(B, C, H, W) bytes, written by a reduction and read by the launch behind it
+ *   `act` is NMSA_BNTAIL_ACT_RELU (act' = 1 where the SAVED OUTPUT y > 0, ATen's threshold backward on the in-place
+ *   result; `aux` is y) or NMSA_BNTAIL_ACT_SILU (z sig(z); act' = sig(z) * (1 + z * (1 - sig(z))) with z RECOMPUTED
+ *   from x, scale and the identity; `aux` is the identity or NULL).
+ *
+ *   Arithmetic: float32 after converting the inputs, every operation above rounded on its own (no contraction
+ *   except where stated); a half output is rounded once, to nearest even.
+ *   Summation order.  A plane is cut into segments of NMSA_BNTAIL_SEGMENT = 2048 consecutive elements; a segment of
+ *   a plane is a UNIT, u = b * segments + segment.  A unit is cut into chunks of V = 4 (float32) / 8 (half)
+ *   elements; lane t of 64 owns chunks t, t + 64, ... of the segment and keeps V partial sums, one per position in
+ *   the chunk, each added in ascending chunk order from 0; they are added pairwise ((a0 + a1) + (a2 + a3)) + ...,
+ *   then the 64 lanes by halves (l += l + 32, 16, 8, 4, 2, 1).
+ *   stats: mean_u = S_u / float(n_u) (IEEE division), then M2_u = sum (x - mean_u)^2 over the SAME values as fused
+ *   multiply-adds in the same order (two passes over registers; never E[x^2] - E[x]^2).
+ *   Merging the U units of a channel: lane l of 64 takes the units l, l + 64, ... in ascending order, then the lanes by
+ *   halves.  (n, mean, M2) pairs merge by Chan's formula, a <- a + b: n = na + nb, d = mb - ma, r = nb / n,
+ *   mean = ma + d * r, M2 = (M2a + M2b) + (d * d) * (na * r); an empty side is skipped.  (sum gu, sum gu * xh) pairs
+ *   merge by addition.  var = M2 / float(M); the running update is rm = (1 - m) * rm + m * mean,
+ *   rv = (1 - m) * rv + m * (M2 / float(M - 1)).  invstd = 1 / sqrt(var + eps), IEEE square root and division.
+ *   The order depends on B, H*W and the dtype only: not on the route, the grid or the device.
+ *
+ * nmsa_bntail_stats: ONE launch; part[c, u] = (mean_u, M2_u).
+ * nmsa_bntail_apply: ONE launch.  part given: training (the partials of nmsa_bntail_stats on the same x are merged by
+ *   every wave; the running statistics are UPDATED; B*H*W below 2: NMSA_ERR_ARG); part NULL: eval (the running
+ *   statistics are READ).  save_mean / save_invstd (both or neither): the statistics the backward pass takes.
+ * nmsa_bntail_bwd_reduce: ONE launch; part[c, u] = (sum gu, sum gu * xh).  With dgamma / dbeta (both or neither) it
+ *   FINISHES ALONE, for a backward pass without a map gradient and for eval mode: one workgroup per channel, the
+ *   same merge, the same bits.
+ * nmsa_bntail_bwd_apply: ONE launch.  part given: the training formula (the partials of nmsa_bntail_bwd_reduce are
+ *   merged by every wave, dgamma / dbeta written when given); part NULL: the eval formula, no sums, dgamma / dbeta
+ *   must be NULL.  A NULL gx / gid: not wanted (nothing wanted: NMSA_OK after the checks, nothing is launched).
+ * No atomics, nothing handed between workgroups inside a launch: two calls on the same inputs give the same bits.
+ * Every kernel launches at most 8 workgroups of 256 lanes per compute unit of nmsa_device_geometry and LOOPS over
+ * the rest of its units, four per workgroup and trip.
+ *
+ * nmsa_bntail_route (host only, nothing is launched, no device is touched): NMSA_BNTAIL_ROUTE_VECTOR (16-byte
+ *   accesses: H*W a multiple of V and EVERY map of the call, t0 .. t4, NULL: not part of it, on 16 bytes) or
+ *   NMSA_BNTAIL_ROUTE_ELEMENT (element-wise accesses, any H*W, any element-aligned pointer); both give the same
+ *   bits.  *segments (may be NULL): the units a plane is cut into.
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a dtype other than
+ * the three, an activation other than the two, B, C, H or W below 1, B*C*H*W of 2^31 or more (32-bit offsets), a
+ * NULL pointer where none is allowed (allowed: identity, scale, save_*, part of apply; aux under SiLU, beta under
+ * ReLU, scale, dgamma, dbeta, gx, gid, part of bwd_apply), only one of a pair, a pointer that is not aligned to
+ * its element, a workspace smaller than nmsa_bntail_workspace_bytes.  No host synchronisation, no allocation;
+ * every call is capturable in a hipGraph as a single chain.
+ * ------------------------------------------------------------------------- */
+#define NMSA_BNTAIL_ACT_RELU 0
+#define NMSA_BNTAIL_ACT_SILU 1
+#define NMSA_BNTAIL_ROUTE_VECTOR 1
+#define NMSA_BNTAIL_ROUTE_ELEMENT 2
+#define NMSA_BNTAIL_SEGMENT 2048
+size_t nmsa_bntail_workspace_bytes(int B, int C, int H, int W);
+int nmsa_bntail_route(const void* t0, const void* t1, const void* t2, const void* t3, const void* t4,
+                      int dtype, int H, int W, int* segments);
+int nmsa_bntail_stats(const void* x, int dtype, int B, int C, int H, int W, float* part,
+                      size_t part_bytes, nmsa_stream_t stream);
+int nmsa_bntail_apply(const void* x, const void* identity, const void* scale, int dtype, int B, int C,
+                      int H, int W, const float* gamma, const float* beta, const float* part,
+                      size_t part_bytes, float* running_mean, float* running_var, float eps,
+                      float momentum, int act, float* save_mean, float* save_invstd, void* y,
+                      nmsa_stream_t stream);
+int nmsa_bntail_bwd_reduce(const void* gy, const void* x, const void* aux, const void* scale, int dtype,
+                           int B, int C, int H, int W, const float* gamma, const float* beta,
+                           const float* mean, const float* invstd, int act, float* part,
+                           size_t part_bytes, float* dgamma, float* dbeta, nmsa_stream_t stream);
+int nmsa_bntail_bwd_apply(const void* gy, const void* x, const void* aux, const void* scale, int dtype,
+                          int B, int C, int H, int W, const float* gamma, const float* beta,
+                          const float* mean, const float* invstd, int act, const float* part,
+                          size_t part_bytes, void* gx, void* gid, float* dgamma, float* dbeta,
+                          nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,10 @@ NMSA_SEFUSE_ROUTE_VECTOR, NMSA_SEFUSE_ROUTE_ELEMENT = 1, 2
 NMSA_SEFUSE_ROUTE_WAVE, NMSA_SEFUSE_ROUTE_BLOCK = 4, 8
 NMSA_SEFUSE_WAVE_PLANE_MAX = 2048
 NMSA_SEFUSE_MAX_CHANNELS = 2048
+# include/nmsa.h: activation codes, route answers and the segment length of the nmsa_bntail_* entry points
+NMSA_BNTAIL_ACT_RELU, NMSA_BNTAIL_ACT_SILU = 0, 1
+NMSA_BNTAIL_ROUTE_VECTOR, NMSA_BNTAIL_ROUTE_ELEMENT = 1, 2
+NMSA_BNTAIL_SEGMENT = 2048
 
 
 class NmsaError(RuntimeError):
@@ -148,6 +152,15 @@ _SIGNATURES = {
     'nmsa_sefuse_weight_grad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'nmsa_sefuse_excite_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'nmsa_sefuse_apply_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'nmsa_bntail_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'nmsa_bntail_route': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'nmsa_bntail_stats': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'nmsa_bntail_apply': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _f, _f, _i,
+                               _vp, _vp, _vp, _vp]),
+    'nmsa_bntail_bwd_reduce': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz,
+                                    _vp, _vp, _vp]),
+    'nmsa_bntail_bwd_apply': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz,
+                                   _vp, _vp, _vp, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

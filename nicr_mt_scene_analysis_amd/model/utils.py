@@ -3,7 +3,8 @@
 reference's sub-module names `conv`, `norm`, `act` (the encoder-decoder fusion's channel adapter);
 `SqueezeAndExcitation`, the channel weighting of the encoder RGB-D fusion, with the reference's
 sub-module layout `layers.{0..3}`.  `model.encoder_fusion` reads its parameters for the fused HIP path
-and calls it as it is everywhere else."""
+and calls it as it is everywhere else;
+`conv3x3` and `conv1x1`, the bias-free convolutions of the residual blocks (`model.block`)."""
 from typing import Optional, Type
 
 import torch.nn.functional as F
@@ -11,6 +12,15 @@ from torch import Tensor, nn
 
 from .activation import get_activation_class
 from .normalization import get_normalization_class
+
+
+def conv3x3(in_planes: int, out_planes: int, stride: int = 1, groups: int = 1, dilation: int = 1) -> nn.Conv2d:
+    return nn.Conv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, groups=groups,
+                     bias=False, dilation=dilation)
+
+
+def conv1x1(in_planes: int, out_planes: int, stride: int = 1) -> nn.Conv2d:
+    return nn.Conv2d(in_planes, out_planes, kernel_size=1, stride=stride, bias=False)
 
 
 class ConvNormAct(nn.Sequential):

@@ -1840,6 +1840,181 @@ def sefuse_route(*tensors: torch.Tensor) -> int:
     return rc
 
 
+# ------------------------------------------------------- residual blocks: the fused batch-norm tail
+_BNTAIL_ACTS = {'relu': L.NMSA_BNTAIL_ACT_RELU, 'silu': L.NMSA_BNTAIL_ACT_SILU}
+
+
+def _bntail_act(act) -> int:
+    if act not in _BNTAIL_ACTS:
+        raise ValueError(f"act must be 'relu' or 'silu', got {act!r}")
+    return _BNTAIL_ACTS[act]
+
+
+def _bntail_maps(first: torch.Tensor, others, names):
+    """dtype code, (B, C, H, W) and the detached maps of a call: `first` sets device, dtype and shape, every
+    tensor of `others` (None allowed) must match it; all must be dense NCHW"""
+    code = _ppm_x_check(first, names[0])
+    shape = tuple(int(n) for n in first.shape)
+    maps = []
+    for t, name in zip((first,) + tuple(others), names):
+        if t is None:
+            maps.append(None)
+            continue
+        _require_on_device(t, name)
+        if t.dtype != first.dtype or tuple(t.shape) != shape or t.device != first.device or not t.is_contiguous():
+            raise TypeError(f'{name} must be a contiguous {first.dtype} {shape} tensor on {first.device}, got '
+                            f'{t.dtype} {tuple(t.shape)} on {t.device}')
+        maps.append(t.detach())
+    return code, shape, maps
+
+
+def _bntail_vec(t: Optional[torch.Tensor], C: int, name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _require_on_device(t, name)
+    if t.dtype != torch.float32 or tuple(t.shape) != (C,) or not t.is_contiguous():
+        raise TypeError(f'{name} must be a contiguous float32 [{C}] tensor, got {t.dtype} {tuple(t.shape)}')
+    return t.detach()
+
+
+def _bntail_scale(scale: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
+    if scale is None:
+        return None
+    B, C = int(like.shape[0]), int(like.shape[1])
+    _require_on_device(scale, 'scale')
+    if scale.dtype != like.dtype or scale.numel() != B * C or tuple(scale.shape[:2]) != (B, C):
+        raise TypeError(f'scale must be {like.dtype} [{B}, {C}] (or [{B}, {C}, 1, 1]), got {scale.dtype} '
+                        f'{tuple(scale.shape)}')
+    return scale.detach().contiguous()
+
+
+def bntail_workspace_bytes(shape) -> int:
+    return int(L.lib().nmsa_bntail_workspace_bytes(*(int(n) for n in shape)))
+
+
+def _bntail_part(part: Optional[torch.Tensor], shape, dev) -> Tuple[torch.Tensor, int]:
+    """the unit partials of a shape: the caller's float32 tensor, or the cached workspace of the stream"""
+    nbytes = bntail_workspace_bytes(shape)
+    if part is None:
+        return _workspace(dev, ('bntail',) + tuple(shape), nbytes)
+    _require_on_device(part, 'part')
+    if part.dtype != torch.float32 or not part.is_contiguous() or part.numel() * 4 < nbytes:
+        raise TypeError(f'part must be a contiguous float32 tensor of at least {nbytes} bytes')
+    return part, part.numel() * 4
+
+
+def bntail_stats(x: torch.Tensor, part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The batch statistics of `x` [B, C, H, W] (float32 / bfloat16 / float16, dense NCHW) as per-unit
+    partials (mean_u, M2_u) in one launch (include/nmsa.h nmsa_bntail_stats): a flat float32 workspace whose
+    first C * U * 2 values are [C, U, 2], U = B * ceil(H*W / L.NMSA_BNTAIL_SEGMENT).  `bntail_apply` merges them.
+    Two passes over registers per unit, Chan's merge between units: no E[x^2] - E[x]^2, no atomics."""
+    code, shape, (xc,) = _bntail_maps(x, (), ('x',))
+    ws, nbytes = _bntail_part(part, shape, xc.device)
+    L.check(L.lib().nmsa_bntail_stats(L.ptr(xc), code, *shape, L.ptr(ws), nbytes, L.stream_ptr(xc.device)),
+            'nmsa_bntail_stats')
+    return ws
+
+
+def bntail_apply(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+                 running_var: torch.Tensor, eps: float, momentum: float = 0.0, act: str = 'relu',
+                 part: Optional[torch.Tensor] = None, identity: Optional[torch.Tensor] = None,
+                 scale: Optional[torch.Tensor] = None, save: bool = False, out: Optional[torch.Tensor] = None):
+    """y = act(((x - mean) * invstd * gamma + beta) * scale[b, c] + identity) in one launch (nmsa_bntail_apply).
+    `part` given (the result of `bntail_stats(x)`): training, the batch statistics; `running_mean` and
+    `running_var` (float32 [C]) are UPDATED in place with `momentum`.  `part` None: eval, they are read.
+    `identity` (x's shape and dtype) and `scale` ([B, C] of x's dtype, the Dropout2d scale) are optional.
+    With `save` returns (y, mean, invstd), the float32 [C] statistics `bntail_backward_*` take."""
+    a = _bntail_act(act)
+    code, shape, (xc, idc) = _bntail_maps(x, (identity,), ('x', 'identity'))
+    B, C, H, W = shape
+    if part is not None and B * H * W < 2:
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {list(shape)}')
+    sc = _bntail_scale(scale, xc)
+    g, b = _bntail_vec(gamma, C, 'gamma'), _bntail_vec(beta, C, 'beta')
+    rm, rv = _bntail_vec(running_mean, C, 'running_mean'), _bntail_vec(running_var, C, 'running_var')
+    y = _sefuse_out(out, shape, xc.dtype, xc.device, 'out')
+    mean = torch.empty((C,), dtype=torch.float32, device=xc.device) if save else None
+    invstd = torch.empty((C,), dtype=torch.float32, device=xc.device) if save else None
+    nbytes = 0
+    if part is not None:
+        part, nbytes = _bntail_part(part, shape, xc.device)
+    L.check(L.lib().nmsa_bntail_apply(L.ptr(xc), L.ptr(idc), L.ptr(sc), code, B, C, H, W, L.ptr(g), L.ptr(b),
+                                      L.ptr(part), nbytes, L.ptr(rm), L.ptr(rv), float(eps), float(momentum), a,
+                                      L.ptr(mean), L.ptr(invstd), L.ptr(y), L.stream_ptr(xc.device)),
+            'nmsa_bntail_apply')
+    return (y, mean, invstd) if save else y
+
+
+def _bntail_bwd_args(gy, x, aux, scale, gamma, beta, mean, invstd, act):
+    a = _bntail_act(act)
+    code, shape, (g, xc, ac) = _bntail_maps(gy, (x, aux), ('gy', 'x', 'aux'))
+    if xc is None or (a == L.NMSA_BNTAIL_ACT_RELU and ac is None):
+        raise TypeError("x is needed, and under 'relu' aux (the saved output y)")
+    C = shape[1]
+    vecs = [_bntail_vec(t, C, n) for t, n in ((gamma, 'gamma'), (beta, 'beta'), (mean, 'mean'), (invstd, 'invstd'))]
+    head = (L.ptr(g), L.ptr(xc), L.ptr(ac), L.ptr(_bntail_scale(scale, g)), code, *shape,
+            *(L.ptr(v) for v in vecs), a)
+    return head, shape, g, (xc, ac, vecs)
+
+
+def bntail_backward_reduce(gy: torch.Tensor, x: torch.Tensor, aux: Optional[torch.Tensor], gamma: torch.Tensor,
+                           beta: Optional[torch.Tensor], mean: torch.Tensor, invstd: torch.Tensor, act: str = 'relu',
+                           scale: Optional[torch.Tensor] = None, finish: bool = False,
+                           part: Optional[torch.Tensor] = None):
+    """The per-unit partials (sum gu, sum gu * xh) of the tail's backward pass in one launch
+    (nmsa_bntail_bwd_reduce); `aux` is the saved output y under 'relu' and the identity (or None) under
+    'silu'.  Returns the workspace `bntail_backward_apply` merges, or with `finish` (dgamma, dbeta) float32 [C],
+    merged by the launch itself in the same order (a backward pass without a map gradient, eval mode)."""
+    head, shape, g, keep = _bntail_bwd_args(gy, x, aux, scale, gamma, beta, mean, invstd, act)
+    ws, nbytes = _bntail_part(part, shape, g.device)
+    dgamma = torch.empty((shape[1],), dtype=torch.float32, device=g.device) if finish else None
+    dbeta = torch.empty((shape[1],), dtype=torch.float32, device=g.device) if finish else None
+    L.check(L.lib().nmsa_bntail_bwd_reduce(*head, L.ptr(ws), nbytes, L.ptr(dgamma), L.ptr(dbeta),
+                                           L.stream_ptr(g.device)), 'nmsa_bntail_bwd_reduce')
+    return (dgamma, dbeta) if finish else ws
+
+
+def bntail_backward_apply(gy: torch.Tensor, x: torch.Tensor, aux: Optional[torch.Tensor], gamma: torch.Tensor,
+                          beta: Optional[torch.Tensor], mean: torch.Tensor, invstd: torch.Tensor, act: str = 'relu',
+                          scale: Optional[torch.Tensor] = None, part: Optional[torch.Tensor] = None,
+                          need_x: bool = True, need_identity: bool = False, need_params: bool = False,
+                          out_x: Optional[torch.Tensor] = None, out_identity: Optional[torch.Tensor] = None):
+    """(gx, gid, dgamma, dbeta) of the tail in one launch (nmsa_bntail_bwd_apply); None for what is not
+    needed.  `part` (the result of `bntail_backward_reduce`): the training formula, and with `need_params`
+    the merged dgamma, dbeta; `part` None: the eval formula gx = gamma * invstd * gu (`need_params` must be
+    False: take them from `bntail_backward_reduce(..., finish=True)`)."""
+    head, shape, g, keep = _bntail_bwd_args(gy, x, aux, scale, gamma, beta, mean, invstd, act)
+    if need_params and part is None:
+        raise ValueError('dgamma and dbeta need the partials of bntail_backward_reduce')
+    nbytes = 0
+    if part is not None:
+        part, nbytes = _bntail_part(part, shape, g.device)
+    gx = _sefuse_out(out_x, shape, g.dtype, g.device, 'out_x') if need_x else None
+    gid = _sefuse_out(out_identity, shape, g.dtype, g.device, 'out_identity') if need_identity else None
+    dgamma = torch.empty((shape[1],), dtype=torch.float32, device=g.device) if need_params else None
+    dbeta = torch.empty((shape[1],), dtype=torch.float32, device=g.device) if need_params else None
+    if need_x or need_identity or need_params:
+        L.check(L.lib().nmsa_bntail_bwd_apply(*head, L.ptr(part), nbytes, L.ptr(gx), L.ptr(gid), L.ptr(dgamma),
+                                              L.ptr(dbeta), L.stream_ptr(g.device)), 'nmsa_bntail_bwd_apply')
+    return gx, gid, dgamma, dbeta
+
+
+def bntail_route(*tensors: torch.Tensor) -> Tuple[int, int]:
+    """(route, segments) of a call of the fused batch-norm tail with these 1..5 [B, C, H, W] maps
+    (`nmsa_bntail_route`): L.NMSA_BNTAIL_ROUTE_VECTOR (16-byte accesses: H*W a multiple of 4 float32 / 8 half
+    elements and every map on 16 bytes) or _ELEMENT, and the units a plane is cut into
+    (ceil(H*W / L.NMSA_BNTAIL_SEGMENT)).  Host only, nothing is launched."""
+    if not 1 <= len(tensors) <= 5 or any(t.ndim != 4 for t in tensors):
+        raise ValueError('1..5 [B, C, H, W] tensors')
+    ptrs = [L.C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (5 - len(tensors))
+    seg = L.C.c_int(0)
+    rc = L.lib().nmsa_bntail_route(*ptrs, L.float_dtype_code(tensors[0]), int(tensors[0].shape[2]),
+                                   int(tensors[0].shape[3]), L.C.byref(seg))
+    if rc < 0:
+        L.check(rc, 'nmsa_bntail_route')
+    return rc, seg.value
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""
