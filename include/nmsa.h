@@ -1086,7 +1086,9 @@ int nmsa_scene_step(const void* logits, int logits_dtype, const void* labels, in
  *   small launch sums them per channel in a fixed order.  No float atomics: two calls on the same
  *   inputs give the same bits.  `workspace` (16-byte aligned, at least
  *   nmsa_upsample2x_dw3x3_bwd_workspace_bytes(B, C, h, w) bytes, any dtype) is needed only with
- *   gweight or gbias; its contents are scratch.
+ *   gweight or gbias; its contents are scratch.  zeropad: the gy of an edge row / column also enters the taps
+ *   that lie on the padding there, times 0: nothing for a finite gy, NaN for a NaN or an infinity, as the
+ *   zero-padded convolution of torch gives.
  * nmsa_upsample2x_dw3x3_route (host only, nothing is launched, no device is touched): the route a
  *   call with these two tensors takes.  NMSA_UP_ROUTE_VECTOR: a lane owns 2 (f32) or 4 (half)
  *   consecutive input pixels and moves 16-byte vectors; taken when w % 2 == 0 (f32) / w % 4 == 0
@@ -1312,7 +1314,8 @@ int nmsa_mlpdec_upcat_bwd(const void* g_out, int dtype, int B, int H, int W, int
  *   W1 f32 [R,C], b1 f32 [R], W2 f32 [C,R], b2 f32 [C] per modality.  `params` is a HOST array of 8
  *   pointers (W1, b1, W2, b2 of rgb, then of depth), `weights` one of 4 (W1, W2 of rgb, then of
  *   depth); both are read during the call and may be reused when it returns.
- *   `act` is NMSA_SEFUSE_ACT_RELU (act' = 0 at z1 <= 0, ATen's threshold backward) or
+ *   `act` is NMSA_SEFUSE_ACT_RELU (h = 0 at z1 <= 0 and z1 elsewhere, a NaN included; gz1 = 0 at z1 <= 0 whatever gh
+ *   is and gh elsewhere, a NaN z1 included: a selection, ATen's threshold backward) or
  *   NMSA_SEFUSE_ACT_SILU (z sig(z); act' = sig(z) * (1 + z * (1 - sig(z)))).
  *
  *   Arithmetic: float32 after converting the inputs; a half output is rounded once, to nearest even.
@@ -1399,8 +1402,9 @@ int nmsa_sefuse_apply_bwd(const void* gy, int dtype, const float* w, const float
  *   gamma, beta, running_mean, running_var, save_mean, save_invstd, mean, invstd, dgamma, dbeta  f32 [C]
  *   part  f32 [C, U, 2], U = B * ceil(H*W / NMSA_BNTAIL_SEGMENT): the caller's workspace of
  *         nmsa_bntail_workspace_bytes(B, C, H, W) bytes, written by a reduction and read by the launch behind it
- *   `act` is NMSA_BNTAIL_ACT_RELU (act' = 1 where the SAVED OUTPUT y > 0, ATen's threshold backward on the in-place
- *   result; `aux` is y) or NMSA_BNTAIL_ACT_SILU (z sig(z); act' = sig(z) * (1 + z * (1 - sig(z))) with z RECOMPUTED
+ *   `act` is NMSA_BNTAIL_ACT_RELU (y = 0 where z <= 0 and z elsewhere, so a NaN z gives NaN as torch.relu does;
+ *   act' = 0 where the SAVED OUTPUT y <= 0 and 1 elsewhere, a NaN y included: ATen's threshold backward on the
+ *   in-place result; `aux` is y) or NMSA_BNTAIL_ACT_SILU (z sig(z); act' = sig(z) * (1 + z * (1 - sig(z))) with z RECOMPUTED
  *   from x, scale and the identity; `aux` is the identity or NULL).
  *
  *   Arithmetic: float32 after converting the inputs, every operation above rounded on its own (no contraction

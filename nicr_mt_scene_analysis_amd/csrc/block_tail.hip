@@ -65,7 +65,7 @@ __device__ __forceinline__ float bnt_sigmoid(float z)
 template <int ACT>
 __device__ __forceinline__ float bnt_act(float z)
 {
-    if constexpr (ACT == NMSA_BNTAIL_ACT_RELU) return z > 0.0f ? z : 0.0f;
+    if constexpr (ACT == NMSA_BNTAIL_ACT_RELU) return z <= 0.0f ? 0.0f : z;     // a NaN passes, as torch.relu's
     else return __fmul_rn(z, bnt_sigmoid(z));
 }
 
@@ -328,7 +328,7 @@ struct BntBwdArgs {
     float count;                // float(M)
 };
 
-// gz and gu of V elements; `aux` is y under ReLU (the gate is y > 0) and the identity (NULL: absent) under
+// gz and gu of V elements; `aux` is y under ReLU (the gate: 0 where y <= 0) and the identity (NULL: absent) under
 // SiLU (z = (xh * gamma + beta) * s + id is recomputed as the forward pass computed it)
 template <int ACT, int V>
 __device__ __forceinline__ void bnt_grad(const float* gy, const float* xh, const float* aux, bool has_aux,
@@ -337,7 +337,7 @@ __device__ __forceinline__ void bnt_grad(const float* gy, const float* xh, const
 #pragma unroll
     for (int j = 0; j < V; ++j) {
         if constexpr (ACT == NMSA_BNTAIL_ACT_RELU) {
-            gz[j] = aux[j] > 0.0f ? gy[j] : 0.0f;
+            gz[j] = aux[j] <= 0.0f ? 0.0f : gy[j];                  // ATen's threshold backward: a NaN y passes gy
         } else {
             float z = __fadd_rn(__fmul_rn(xh[j], ch.gamma), ch.beta);
             if (has_scale) z = __fmul_rn(z, ch.scale);

@@ -80,18 +80,19 @@ __device__ __forceinline__ float sef_sigmoid(float z)
 template <int ACT>
 __device__ __forceinline__ float sef_act(float z)
 {
-    if constexpr (ACT == NMSA_SEFUSE_ACT_RELU) return z > 0.0f ? z : 0.0f;
+    if constexpr (ACT == NMSA_SEFUSE_ACT_RELU) return z <= 0.0f ? 0.0f : z;     // a NaN passes, as torch.relu's
     else return __fmul_rn(z, sef_sigmoid(z));
 }
 
-// act'(z): ReLU 0 at z <= 0 (ATen's threshold backward); SiLU sig * (1 + z * (1 - sig))
+// g * act'(z).  ReLU: ATen's threshold backward, a selection (0 at z <= 0 whatever g is, g at a NaN z);
+// SiLU: g * (sig * (1 + z * (1 - sig)))
 template <int ACT>
-__device__ __forceinline__ float sef_act_grad(float z)
+__device__ __forceinline__ float sef_act_grad(float g, float z)
 {
-    if constexpr (ACT == NMSA_SEFUSE_ACT_RELU) return z > 0.0f ? 1.0f : 0.0f;
+    if constexpr (ACT == NMSA_SEFUSE_ACT_RELU) return z <= 0.0f ? 0.0f : g;
     else {
         const float sg = sef_sigmoid(z);
-        return __fmul_rn(sg, __fadd_rn(1.0f, __fmul_rn(z, __fsub_rn(1.0f, sg))));
+        return __fmul_rn(g, __fmul_rn(sg, __fadd_rn(1.0f, __fmul_rn(z, __fsub_rn(1.0f, sg)))));
     }
 }
 
@@ -298,7 +299,7 @@ __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_excite_bwd(
         acc = wave_reduce_sum(acc);
         if (lane_id() == 0) {
             const float z = z1[(size_t)mb * R + r];
-            const float g = __fmul_rn(acc, sef_act_grad<ACT>(z));
+            const float g = sef_act_grad<ACT>(acc, z);
             gz1[(size_t)mb * R + r] = g;
             h[(size_t)mb * R + r] = sef_act<ACT>(z);
             sh_z[r] = g;

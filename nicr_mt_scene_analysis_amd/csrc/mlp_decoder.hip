@@ -111,7 +111,9 @@ __device__ __forceinline__ bool mld_reads(int mode, float scale, int dst, int in
 
 // a range of output indices that holds every one that reads `cell` at factor f = 1 << sh (members are
 // tested exactly): nearest f*cell .. f*cell + f - 1; bilinear i0 == cell for f*cell + f/2 ..
-// f*cell + 3f/2 - 1 and i1 == cell for the f indices below, the border clamps stay inside [0, out)
+// f*cell + 3f/2 - 1 and i1 == cell for the f indices below; cell 1 is also the i1 of the f/2 indices at the border
+// whose source clamps to 0 (weight 0: nothing for a finite gradient, NaN for a NaN or an infinity, as ATen's
+// backward gives); the border clamps stay inside [0, out)
 __device__ __forceinline__ void mld_readers(int mode, int sh, int out, int cell, int& lo, int& hi)
 {
     const int f = 1 << sh, a = cell << sh;
@@ -119,7 +121,7 @@ __device__ __forceinline__ void mld_readers(int mode, int sh, int out, int cell,
         lo = a;
         hi = a + f - 1;
     } else {
-        lo = max(a - (f >> 1), 0);
+        lo = cell == 1 ? 0 : max(a - (f >> 1), 0);
         hi = min(a + f + (f >> 1) - 1, out - 1);
     }
 }

@@ -266,6 +266,25 @@ __global__ __launch_bounds__(UP_THREADS) void k_up_bwd(
                             acc[6 + j] = __fmaf_rn(xv[p], P2, acc[6 + j]);
                         }
                     }
+                    if (partials && g.zeropad) {
+                        // the zero-padded convolution multiplies the gy of an edge row / column by the padded
+                        // zeros: nothing for a finite gy, NaN for a NaN or an infinity, as in torch's gweight.
+                        // Every gy is multiplied on its own: a sum of large finite values first could overflow
+                        const bool zt = r == 0, zb = r == g.h - 1, zl = s0 + p == 0, zr = s0 + p == g.w - 1;
+                        if (zt || zb || zl || zr) {
+                            const float z11 = __fmul_rn(0.0f, win[1][b0 + 1]), z12 = __fmul_rn(0.0f, win[1][b0 + 2]);
+                            const float z21 = __fmul_rn(0.0f, win[2][b0 + 1]), z22 = __fmul_rn(0.0f, win[2][b0 + 2]);
+                            float rowz[3] = {0.0f, 0.0f, 0.0f}, colz[3] = {0.0f, 0.0f, 0.0f};
+                            if (zt) rowz[0] = z11 + z12;        // gy row 0 under the taps i = 0
+                            if (zb) rowz[2] = z21 + z22;        // gy row 2h-1 under i = 2
+                            if (zl) colz[0] = z11 + z21;        // gy column 0 under j = 0
+                            if (zr) colz[2] = z12 + z22;        // gy column 2w-1 under j = 2
+#pragma unroll
+                            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                                for (int j = 0; j < 3; ++j) acc[3 * i + j] += rowz[i] + colz[j];
+                        }
+                    }
                     out[p] = gxv;
                     acc[9] += (win[1][b0 + 1] + win[1][b0 + 2]) + (win[2][b0 + 1] + win[2][b0 + 2]);
                 }

@@ -14,7 +14,8 @@ The batch-norm tail on the device.  Every norm-to-activation segment of a block,
   NonBottleneck1D   norm1 -> act1_2; norm2 -> dropout -> (+ identity) -> act2_2
 is ONE autograd node, `BatchNormTailFunction`: at most two HIP launches forward (`ops.bntail_stats`,
 `ops.bntail_apply`; one in eval mode) and two backward (`ops.bntail_backward_reduce`,
-`ops.bntail_backward_apply`).  It saves x, the output y (ReLU: the gate is y > 0) or the identity (SiLU: z is
+`ops.bntail_backward_apply`).  It saves x, the output y (ReLU: the gate is 0 where y <= 0, so a NaN
+y passes the gradient as ATen's threshold backward does) or the identity (SiLU: z is
 recomputed), the Dropout2d scale [B, C] and per-channel vectors; the normalised map, the dropout product and
 the sum are never written.  The `norm*` sub-modules stay the `nn.BatchNorm2d` modules `normalization(planes)`
 returns: the fused path reads their parameters and buffers and writes their running statistics.  The

@@ -23,7 +23,8 @@ restated square carries too.  A variance from E[x^2] - E[x]^2 has the error U E[
 bound as soon as the mean is large against the deviation.
 ReLU is 1-Lipschitz (e passes through); SiLU is 1.1-Lipschitz and SiLU' 0.5-Lipschitz, and their own
 evaluation (expf within 2 ulp, a division, one to four products) costs SILU_K = 8 roundings of the largest
-intermediate.  The ReLU gate of the backward pass is taken from the VALUE of the output: a bound through a
+intermediate.  The ReLU gate of the backward pass is taken from the VALUE of the output (0 where y <= 0, so a NaN y passes
+gy as a NaN z passes the forward, both as ATen does): a bound through a
 gate holds where the gate cannot flip, which the tests that chain forward and backward assert on their
 inputs (`block_reference`, 'margins'); the per-kernel backward tests hand y in as an input.
 A half output is rounded once more, by half an ulp: 2^-8 relative (bfloat16, 8 significand bits) or 2^-11
@@ -104,8 +105,9 @@ class E:
     def sum(self, dims, depth):
         return E(self.v.sum(dims), self.e.sum(dims) + depth * U * self.v.abs().sum(dims))
 
-    def where(self, mask):
-        return E(self.v * mask, self.e * mask)
+    def zero_where(self, mask):
+        """0 where `mask`, self elsewhere (a selection, not a product: inf and NaN under the mask give 0)"""
+        return E(torch.where(mask, torch.zeros_like(self.v), self.v), torch.where(mask, torch.zeros_like(self.e), self.e))
 
     def rounded(self, dtype):
         h = HALF_U[dtype]
@@ -130,13 +132,13 @@ def silu_grad(z: E) -> E:
 
 def act_forward(z: E, act: str) -> E:
     if act == 'relu':
-        return z.where((z.v > 0).double())
+        return z.zero_where(z.v <= 0)                               # torch.relu: a NaN z passes
     return silu(z) if act == 'silu' else z
 
 
 def act_backward(gy: E, z: E, y: E, act: str) -> E:
     if act == 'relu':
-        return gy.where((y.v > 0).double())
+        return gy.zero_where(y.v <= 0)                              # ATen's threshold backward: a NaN y passes gy
     return gy * silu_grad(z) if act == 'silu' else gy
 
 

@@ -50,7 +50,7 @@ def _act(z, act):
 
 def _act_grad(z, act):
     if act == 'relu':
-        return (z > 0).double()
+        return 1.0 - (z <= 0).double()                              # ATen's threshold backward: 1 at a NaN z
     sg = _sig(z)
     return sg * (1.0 + z * (1.0 - sg))
 
@@ -148,7 +148,8 @@ def excite_backward64(gw, w, z1, params, act, defect=None):
     for m, (W1, b1, W2, b2) in enumerate(params64(params)):
         gh.append(gz2[m] @ W2)
     gh = torch.stack(gh)
-    gz1 = gh * _act_grad(z64, act)
+    # ReLU: ATen's threshold backward selects (0 at z <= 0 whatever gh is), SiLU multiplies
+    gz1 = torch.where(z64 <= 0, torch.zeros_like(gh), gh) if act == 'relu' else gh * _act_grad(z64, act)
     for m, (W1, b1, W2, b2) in enumerate(params64(params)):
         gs.append(gz1[m] @ W1)
     return {'gz2': gz2, 'gh': gh, 'gz1': gz1, 'gs': torch.stack(gs), 'h': _act(z64, act)}

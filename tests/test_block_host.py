@@ -15,6 +15,7 @@ from nicr_mt_scene_analysis_amd.model import block as block_module
 from nicr_mt_scene_analysis_amd.model.utils import conv1x1, conv3x3
 from nicr_mt_scene_analysis_amd.testing import block_cases as BC
 from nicr_mt_scene_analysis_amd.testing import block_ref as R
+from nicr_mt_scene_analysis_amd.testing import nonfinite as NF
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'block.npz')
 RECORDS = BC.golden_records()
@@ -203,3 +204,40 @@ def test_cpu_tensors_never_touch_the_library(monkeypatch):
         assert x.grad is not None
     with pytest.raises(ValueError):
         model.BasicBlock(4, 4)(torch.randn(1, 4, 1, 1))                           # torch's own refusal of M == 1
+
+
+# ------------------------------------------------------------------------------ non-finite values
+def test_restated_relu_passes_nan_and_maps_infinities_as_aten_does():
+    nan, inf = float('nan'), float('inf')
+    z = torch.tensor([nan, inf, -inf, -1.0, 0.0, 2.0], dtype=torch.float64)
+    gy = torch.tensor([3.0, 4.0, inf, nan, 5.0, 6.0], dtype=torch.float64)
+    y = R.act_forward(R.E(z), 'relu')
+    want_y = torch.relu(z)
+    assert torch.equal(torch.isnan(y.v), torch.isnan(want_y)) and torch.equal(y.v[1:], want_y[1:])
+    assert torch.isnan(y.v[0]) and float(y.v[2]) == 0.0 and float(y.e[2]) == 0.0
+    gz = R.act_backward(R.E(gy), None, y, 'relu')
+    zz = z.clone().requires_grad_(True)
+    want_gz = torch.autograd.grad(torch.relu(zz), zz, gy)[0]
+    assert torch.equal(gz.v.nan_to_num(nan=-7.0), want_gz.nan_to_num(nan=-7.0))
+    assert float(gz.v[0]) == 3.0 and float(gz.v[2]) == 0.0 and float(gz.v[3]) == 0.0     # a NaN y passes gy; closed gates give 0
+
+
+@pytest.mark.parametrize('case', NF.block_cases(), ids=repr)
+def test_nonfinite_cases_show_the_poison_and_contain_it_in_the_composition(case):
+    """the condition that keeps tests/test_nonfinite_model.py honest, on the composition alone: in every poisoned
+    run an output element is touched and one is not, and a NaN and a +inf leave a non-finite output"""
+    for dtype in NF.DTYPES:
+        assert NF.run(case, dtype) == 9 * len(case.maps)
+
+
+def test_a_poisoned_training_channel_is_non_finite_as_a_whole_and_alone():
+    case = next(c for c in NF.block_cases() if c.id == 'block-2x16x15x20-relu-forward/train-scale+id')
+    clean = case.make(torch.float32)
+    index = case.places('x', clean['x'], torch.float32)[2]
+    channel = index // (15 * 20) % 16
+    for value in NF.POISONS.values():
+        out, _ = case.comp(NF.to64(NF.place(clean, 'x', index, value)))
+        for key in ('y', 'mean', 'invstd', 'running_mean', 'running_var'):
+            bad = ~torch.isfinite(out[key])
+            bad = bad.flatten(2).all(2).all(0) if key == 'y' else bad
+            assert bad.tolist() == [c == channel for c in range(16)], key

@@ -246,3 +246,15 @@ def test_the_exact_tier_is_exact_in_float32_on_the_cpu():
             assert torch.equal(cat.double(), ref['cat']) and torch.equal(xr.grad.double(), ref['gx_pool'])
             assert all(torch.equal(y.grad.double(), r) for y, r in zip(yr, ref['gys']))
     assert not R.is_power_of_two_geometry((15, 20), cc.sizes_of((1, 5)))
+
+
+# ------------------------------------------------------------------------------ non-finite values
+from nicr_mt_scene_analysis_amd.testing import nonfinite as NF      # noqa: E402
+
+
+@pytest.mark.parametrize('case', NF.ppm_cases(), ids=repr)
+def test_nonfinite_cases_show_the_poison_and_contain_it_in_the_composition(case):
+    """the condition that keeps tests/test_nonfinite_model.py honest, on the composition alone: in every poisoned
+    run an output element is touched and one is not, and a NaN and a +inf leave a non-finite output"""
+    for dtype in NF.DTYPES:
+        assert NF.run(case, dtype) > 0

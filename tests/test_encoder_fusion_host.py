@@ -13,6 +13,7 @@ from nicr_mt_scene_analysis_amd.model.activation import get_activation_class
 from nicr_mt_scene_analysis_amd.model.utils import SqueezeAndExcitation
 from nicr_mt_scene_analysis_amd.testing import encoder_fusion_cases as EC
 from nicr_mt_scene_analysis_amd.testing import encoder_fusion_ref as R
+from nicr_mt_scene_analysis_amd.testing import nonfinite as NF
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'encoder_fusion.npz')
 CHECKED = ('s', 'z1', 'h', 'w', 'y', 'gw', 'gz2', 'gz1', 'gs', 'gx_rgb', 'gx_depth') + R.PARAM_GRADS
@@ -219,3 +220,32 @@ def test_sigmoid_roundoff_is_measured_not_assumed():
     K = R.sigmoid_roundoff(z)
     assert 3.0 <= K < 64.0, K
     assert R.sigmoid_roundoff(torch.zeros(4, dtype=torch.float64)) == 3.0
+
+
+# ------------------------------------------------------------------------------ non-finite values
+def test_restated_relu_gradient_is_one_at_a_nan_as_aten_gives():
+    nan, inf = float('nan'), float('inf')
+    z = torch.tensor([nan, inf, -inf, -1.0, 0.0, 2.0], dtype=torch.float64)
+    zz = z.clone().requires_grad_(True)
+    want = torch.autograd.grad(torch.relu(zz), zz, torch.ones_like(z))[0]
+    assert torch.equal(R._act_grad(z, 'relu'), want) and want.tolist() == [1.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+    assert torch.isnan(R._act(z, 'relu')[0]) and R._act(z, 'relu')[1:].tolist() == [inf, 0.0, 0.0, 0.0, 2.0]
+
+
+@pytest.mark.parametrize('case', NF.sefuse_cases(), ids=repr)
+def test_nonfinite_cases_show_the_poison_and_contain_it_in_the_composition(case):
+    """the condition that keeps tests/test_nonfinite_model.py honest, on the composition alone: in every poisoned
+    run an output element is touched and one is not, and a NaN and a +inf leave a non-finite output"""
+    for dtype in NF.DTYPES:
+        assert NF.run(case, dtype) == 27
+
+
+@pytest.mark.parametrize('act', EC.ACTS)
+def test_a_nan_poisons_every_channel_of_its_image_and_modality_only(act):
+    case = next(c for c in NF.sefuse_cases() if c.id == f'sefuse-48x15x20-{act}')
+    clean = case.make(torch.float32)
+    index = case.places('x_rgb', clean['x_rgb'], torch.float32)[2]                  # image 1
+    out, _ = case.comp(NF.to64(NF.place(clean, 'x_rgb', index, float('nan'))))
+    assert bool(torch.isnan(out['w'][0, 1]).all()) and bool(torch.isfinite(out['w'][0, 0]).all())
+    assert bool(torch.isfinite(out['w'][1]).all())
+    assert bool(torch.isnan(out['y'][1]).all()) and bool(torch.isfinite(out['y'][0]).all())

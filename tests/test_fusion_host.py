@@ -195,3 +195,15 @@ def test_backward_workspace_follows_the_assumed_compute_units(monkeypatch, cus):
             for B, P in ((1, 32 * tiles), (1, 32 * tiles - 31)) + (((2, 16 * tiles),) if tiles % 2 == 0 else ()):
                 assert B * -(-P // 32) == tiles
                 assert query(B, P, C) == min(tiles, cap) * 2 * C * 4, (cus, C, B, P)
+
+
+# ------------------------------------------------------------------------------ non-finite values
+from nicr_mt_scene_analysis_amd.testing import nonfinite as NF      # noqa: E402
+
+
+@pytest.mark.parametrize('case', NF.lnt_cases(), ids=repr)
+def test_nonfinite_cases_show_the_poison_and_contain_it_in_the_composition(case):
+    """the condition that keeps tests/test_nonfinite_model.py honest, on the composition alone: in every poisoned
+    run an output element is touched and one is not, and a NaN and a +inf leave a non-finite output"""
+    for dtype in NF.LNT_PAIRS:
+        assert NF.run(case, dtype) > 0

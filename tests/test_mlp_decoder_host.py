@@ -272,3 +272,15 @@ def test_defective_restatements_fall_outside_the_bounds(mode, defect):
     # the branch that already has the output size is untouched by either defect
     for i in range(3):
         assert R.worst_ratio(bad_gys[i], ref['gys'][i], bd['gys'][i]) > 1.0, i
+
+
+# ------------------------------------------------------------------------------ non-finite values
+from nicr_mt_scene_analysis_amd.testing import nonfinite as NF      # noqa: E402
+
+
+@pytest.mark.parametrize('case', NF.mld_cases(), ids=repr)
+def test_nonfinite_cases_show_the_poison_and_contain_it_in_the_composition(case):
+    """the condition that keeps tests/test_nonfinite_model.py honest, on the composition alone: in every poisoned
+    run an output element is touched and one is not, and a NaN and a +inf leave a non-finite output"""
+    for dtype in NF.DTYPES:
+        assert NF.run(case, dtype) > 0

@@ -159,3 +159,15 @@ def test_fixture_digests_match_the_regenerated_cases():
         assert g[f'{name}__y'].shape == (B, C, 2 * h, 2 * w) and g[f'{name}__gx'].shape == shape
         assert g[f'{name}__gw'].shape == (C, 1, 3, 3) and ((f'{name}__gb' in g.files) == use_bias)
         assert g[f'{name}__y'].dtype == np.float32
+
+
+# ------------------------------------------------------------------------------ non-finite values
+from nicr_mt_scene_analysis_amd.testing import nonfinite as NF      # noqa: E402
+
+
+@pytest.mark.parametrize('case', NF.up_cases(), ids=repr)
+def test_nonfinite_cases_show_the_poison_and_contain_it_in_the_composition(case):
+    """the condition that keeps tests/test_nonfinite_model.py honest, on the composition alone: in every poisoned
+    run an output element is touched and one is not, and a NaN and a +inf leave a non-finite output"""
+    for dtype in NF.DTYPES:
+        assert NF.run(case, dtype) > 0
