@@ -1474,6 +1474,52 @@ int nmsa_bntail_bwd_apply(const void* gy, const void* x, const void* aux, const 
                           size_t part_bytes, void* gx, void* gid, float* dgamma, float* dbeta,
                           nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * the stem max pool of the ResNet backbones (csrc/maxpool.hip)
+ *     model/backbone/resnet.py, `maxpool` = nn.MaxPool2d(kernel_size=3, stride=2, padding=1): dilation 1, floor
+ *     mode, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.
+ *
+ *   x, gx   [B,C,H,W]    NMSA_F32 | NMSA_BF16 | NMSA_F16, contiguous; ONE dtype per call
+ *   y, gy   [B,C,Ho,Wo]  the same dtype
+ *   code    u8 [B,C,Ho,Wo]: 3 * (r - (2 oy - 1)) + (c - (2 ox - 1)), 0..8, the window position of the input pixel
+ *           (r, c) that ATen's max_pool2d_with_indices names with its int64 index r * W + c
+ *
+ *   Selection (ATen's rule, explicit comparisons, no fmax): the window positions inside the map in row-major
+ *   order, starting at the first, the choice replaced when `val > max || isnan(val)`.  Ties, signed zeros
+ *   included, keep the first position; a window holding NaNs selects its last NaN; an all -inf window its first
+ *   position.  y carries the selected element's bits.
+ *
+ * nmsa_maxpool3x3s2_fwd: ONE launch, x read once, y written once, no workspace.  `code` may be NULL: no code is
+ *   written (inference).
+ * nmsa_maxpool3x3s2_bwd: ONE launch in gather form.  gx[r,c] = the sum of gy[oy,ox] over the at most four windows
+ *   that cover (r, c) and whose code points at it, oy ascending, then ox ascending, added in float32 from 0; a
+ *   half output is rounded once, to nearest even.  EVERY gx element is written (no memset is needed), no atomics:
+ *   two calls on the same inputs give the same bits.  A code above 8 points nowhere.
+ * nmsa_maxpool3x3s2_route (host only, nothing is launched, no device is touched): the route a call with these two
+ *   tensors takes.  NMSA_MP_ROUTE_VECTOR: a lane owns 2 (f32) or 4 (half) consecutive output pixels and moves its
+ *   4 / 8 input (gx) elements of a row as one 16-byte vector; taken when W % 4 == 0 (f32) / W % 8 == 0 (half) and
+ *   EVERY tensor of the call (x, y and code; gy, code and gx) starts on 16 bytes.  NMSA_MP_ROUTE_PIXEL: one
+ *   output pixel per lane, element-wise accesses, any width and any element-aligned pointer.  Both give the
+ *   same bits.  `x` is an input-sized tensor of the call, `y_or_gx` another of its tensors (the call takes the
+ *   vector route when every answer is NMSA_MP_ROUTE_VECTOR).
+ * Every kernel launches at most 8 workgroups of 256 lanes per compute unit of nmsa_device_geometry and LOOPS over
+ * the rest of the planes and tiles.
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a NULL x / y / gy /
+ * gx, a NULL code in the backward call, a dtype other than the three, B, C, H or W below 1, a pointer that is
+ * not aligned to its element.  NMSA_ERR_UNSUPPORTED: a plane of 2^31 elements or more (H W; offsets inside a
+ * plane are 32-bit, the plane base is 64-bit, so B*C*H*W may exceed 2^31), B*C above 2^31 - 1, 2^31 or more lane
+ * units (B*C * ceil(Ho / 8) * Wo on the one-pixel route).  No host synchronisation, no allocation; capturable in
+ * a hipGraph as a single chain.
+ * ------------------------------------------------------------------------- */
+#define NMSA_MP_ROUTE_VECTOR 1
+#define NMSA_MP_ROUTE_PIXEL 2
+int nmsa_maxpool3x3s2_route(const void* x, const void* y_or_gx, int dtype, int B, int C, int H, int W);
+int nmsa_maxpool3x3s2_fwd(const void* x, int dtype, int B, int C, int H, int W, void* y, uint8_t* code,
+                          nmsa_stream_t stream);
+int nmsa_maxpool3x3s2_bwd(const void* gy, const uint8_t* code, int dtype, int B, int C, int H, int W, void* gx,
+                          nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ NMSA_SEFUSE_MAX_CHANNELS = 2048
 NMSA_BNTAIL_ACT_RELU, NMSA_BNTAIL_ACT_SILU = 0, 1
 NMSA_BNTAIL_ROUTE_VECTOR, NMSA_BNTAIL_ROUTE_ELEMENT = 1, 2
 NMSA_BNTAIL_SEGMENT = 2048
+# include/nmsa.h: answers of nmsa_maxpool3x3s2_route
+NMSA_MP_ROUTE_VECTOR, NMSA_MP_ROUTE_PIXEL = 1, 2
 
 
 class NmsaError(RuntimeError):
@@ -161,6 +163,9 @@ _SIGNATURES = {
                                     _vp, _vp, _vp]),
     'nmsa_bntail_bwd_apply': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz,
                                    _vp, _vp, _vp, _vp, _vp]),
+    'nmsa_maxpool3x3s2_route': (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
+    'nmsa_maxpool3x3s2_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'nmsa_maxpool3x3s2_bwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

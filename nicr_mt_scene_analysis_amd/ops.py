@@ -2015,6 +2015,77 @@ def bntail_route(*tensors: torch.Tensor) -> Tuple[int, int]:
     return rc, seg.value
 
 
+# ------------------------------------------------------------- the stem max pool of the ResNet backbones
+def maxpool3x3s2_out_shape(shape) -> Tuple[int, int, int, int]:
+    B, C, H, W = (int(n) for n in shape)
+    return B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+def _mp_check(x: torch.Tensor, name: str) -> int:
+    code = _ppm_x_check(x, name)
+    if not x.is_contiguous():
+        raise TypeError(f'{name} must be dense NCHW, got strides {tuple(x.stride())}')
+    return code
+
+
+def maxpool3x3s2(x: torch.Tensor, need_code: bool = True, out: Optional[torch.Tensor] = None):
+    """`F.max_pool2d(x, 3, 2, 1)` in one launch (include/nmsa.h nmsa_maxpool3x3s2_fwd).  `x` [B, C, H, W] float32
+    / bfloat16 / float16, dense NCHW on the device.  Returns (y, code): y [B, C, Ho, Wo] in x's dtype carries the
+    selected elements' bits (ATen's selection rule: first maximum, last NaN); code uint8 of y's shape is the
+    window position 0..8 of the selected pixel, what `maxpool3x3s2_backward` reads in place of ATen's int64 index.
+    Without `need_code` (inference) none is allocated or written and None is returned for it.  No autograd:
+    that is `model.pooling.MaxPool3x3S2Function`."""
+    code = _mp_check(x, 'x')
+    xc = x.detach()
+    B, C, H, W = (int(n) for n in xc.shape)
+    oshape = maxpool3x3s2_out_shape(xc.shape)
+    y = _sefuse_out(out, oshape, xc.dtype, xc.device, 'out')
+    k = torch.empty(oshape, dtype=torch.uint8, device=xc.device) if need_code else None
+    L.check(L.lib().nmsa_maxpool3x3s2_fwd(L.ptr(xc), code, B, C, H, W, L.ptr(y), L.ptr(k), L.stream_ptr(xc.device)),
+            'nmsa_maxpool3x3s2_fwd')
+    return y, k
+
+
+def maxpool3x3s2_backward(gy: torch.Tensor, code: torch.Tensor, input_hw: Tuple[int, int],
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gx [B, C, H, W] of `maxpool3x3s2` for the upstream gradient `gy` [B, C, Ho, Wo] and the forward's `code`
+    in one launch (nmsa_maxpool3x3s2_bwd): a gather, every element written, float32 sums in a fixed order
+    (oy, then ox, ascending) rounded once: the same bits on every call."""
+    dcode = _mp_check(gy, 'gy')
+    H, W = (int(n) for n in input_hw)
+    B, C = int(gy.shape[0]), int(gy.shape[1])
+    oshape = maxpool3x3s2_out_shape((B, C, H, W))
+    _require_on_device(code, 'code')
+    if tuple(gy.shape) != oshape or tuple(code.shape) != oshape or code.dtype != torch.uint8 \
+            or not code.is_contiguous() or code.device != gy.device:
+        raise TypeError(f'gy and code (uint8, contiguous) must be {oshape} for an input of {H}x{W}, got '
+                        f'{tuple(gy.shape)} and {code.dtype} {tuple(code.shape)}')
+    g = gy.detach()
+    gx = _sefuse_out(out, (B, C, H, W), g.dtype, g.device, 'out')
+    L.check(L.lib().nmsa_maxpool3x3s2_bwd(L.ptr(g), L.ptr(code), dcode, B, C, H, W, L.ptr(gx), L.stream_ptr(g.device)),
+            'nmsa_maxpool3x3s2_bwd')
+    return gx
+
+
+def maxpool3x3s2_route(x: torch.Tensor, *others: torch.Tensor) -> int:
+    """The route a call with these tensors takes (`nmsa_maxpool3x3s2_route`, asked once per other tensor):
+    L.NMSA_MP_ROUTE_VECTOR when every answer is, else L.NMSA_MP_ROUTE_PIXEL.  `x` [B, C, H, W] is an
+    input-sized tensor of the call (x or gx), `others` its remaining tensors (y and code; gy and code).  Only
+    shapes, the dtype and the addresses are looked at, nothing is launched."""
+    if x.ndim != 4 or not others:
+        raise ValueError('an input-sized [B, C, H, W] tensor and at least one more tensor of the call')
+    B, C, H, W = (int(n) for n in x.shape)
+    route = L.NMSA_MP_ROUTE_VECTOR
+    for t in others:
+        rc = L.lib().nmsa_maxpool3x3s2_route(L.C.c_void_p(x.data_ptr()), L.C.c_void_p(t.data_ptr()),
+                                             L.float_dtype_code(x), B, C, H, W)
+        if rc < 0:
+            L.check(rc, 'nmsa_maxpool3x3s2_route')
+        if rc != L.NMSA_MP_ROUTE_VECTOR:
+            route = L.NMSA_MP_ROUTE_PIXEL
+    return route
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""
