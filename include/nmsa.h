@@ -527,9 +527,10 @@ int nmsa_pq_update_with_confmat_parts(
  *     target u8 [B,H,W], 0 = void (ignored); weights f32 [C] or NULL;
  *     weight_sum (f64, may be NULL) = sum over non-void px of w[label]: the divisor
  *     of the ESANet `weighted_reduction` (ce.py:57-68);
- *     lse2 f32 [B,H,W] (optional, NULL = off): the forward pass stores -log2(sum_c exp(x_c))
- *     per pixel and the backward pass, given the same buffer, reads the logits ONCE
- *     instead of twice (what autograd's saved log_softmax buys the reference)
+ *     lse2 f32 [2,B,H,W] (optional, NULL = off): the forward pass stores max_c x_c (plane 0) and
+ *     log2(sum_c exp(x_c - max)) (plane 1) per pixel and the backward pass, given the same buffer,
+ *     reads the logits ONCE instead of twice (what autograd's saved log_softmax buys the
+ *     reference); two planes, since one float max * log2(e) + log2(sum) rounds to an ulp of |max|
  * nmsa_loss_masked_*   MSELoss / L1Loss (reduction='sum') loss/mse.py:21-41, l1.py:21-41
  *     with the masking of task_helper/instance.py:129-139,154-167:
  *     sum_px mean_c f(pred*mask - target), n = sum(mask); mask u8 [B,H,W] or NULL;
@@ -570,6 +571,7 @@ int nmsa_pq_update_with_confmat_parts(
  *     the prediction ONCE (for the gradient) instead of twice
  * ------------------------------------------------------------------------- */
 size_t nmsa_loss_workspace_bytes(int B, int H, int W);
+/* NaN / +-inf logits: the classes of F.cross_entropy(ignore_index=-1), a void pixel's column included */
 int nmsa_loss_ce_fwd(const void* logits, int dtype, const uint8_t* target, const float* weights,
                      int B, int C, int H, int W, float label_smoothing,
                      double* loss_sum, int64_t* n_elements, double* weight_sum, float* lse2_out,
@@ -592,6 +594,7 @@ int nmsa_loss_ce_bwd_i16(const void* logits, int dtype, const int16_t* target,
                          float label_smoothing, const float* grad_scale, const float* lse2,
                          void* grad_logits, nmsa_stream_t stream);
 int nmsa_loss_ce_fwd_grad_supported(int dtype, int C);
+/* pinned as nmsa_loss_ce_fwd / _bwd: loss and gradient classes of F.cross_entropy; exponents are (x - max) * log2(e), finite logits up to 1e30 are pinned */
 int nmsa_loss_ce_fwd_grad(const void* logits, int dtype, const uint8_t* target, const float* weights,
                           int B, int C, int H, int W, float label_smoothing,
                           const float* expected_grad_scale,
@@ -606,6 +609,8 @@ size_t nmsa_count_workspace_bytes(void);
 int nmsa_count_u8(const uint8_t* values, int64_t n, int lo, int hi, int64_t* count,
                   float* mean_scale, float weight,
                   void* workspace, size_t workspace_bytes, nmsa_stream_t stream);
+/* a masked-out pixel is never read: a NaN / infinity there leaves sum, count and gradient clean (the reference multiplies: NaN); kind 2 (focal) clamps by
+ * comparisons, so a NaN prediction gives a NaN sum and a zero gradient at its element, +-inf are clamped */
 int nmsa_loss_masked_fwd(const void* pred, int dtype, const float* target, const uint8_t* mask,
                          int B, int C, int H, int W, int kind,
                          double* loss_sum, int64_t* n_mask,
@@ -622,6 +627,7 @@ int nmsa_loss_masked_bwd_unless(const void* pred, int dtype, const float* target
                                 const uint8_t* mask, int B, int C, int H, int W, int kind,
                                 const float* grad_scale, void* grad_pred,
                                 const float* computed_for, int32_t* counters, nmsa_stream_t stream);
+/* a masked-out pixel is never read; NaN / +-inf at a masked one answer as 1 - exp(kappa (x.y - 1)) does */
 int nmsa_loss_vonmises_fwd(const void* pred, int dtype, const float* target, const uint8_t* mask,
                            int B, int H, int W, float kappa,
                            double* loss_sum, int64_t* n_rows,
@@ -639,6 +645,7 @@ int nmsa_loss_vonmises_bwd_unless(const void* pred, int dtype, const float* targ
                                   const float* grad_scale, void* grad_pred,
                                   const float* computed_for, int32_t* counters,
                                   nmsa_stream_t stream);
+/* a pixel with index 0 is never read: a NaN / infinity there leaves sum, count and gradient clean, its gradient column exactly 0 */
 int nmsa_loss_cos_emb_fwd(const void* pred, int dtype, const int32_t* indices, const float* lut,
                           int B, int D, int H, int W, int L,
                           double* loss_sum, int64_t* n_rows, float* dots_out, int32_t* status,
@@ -692,6 +699,7 @@ int nmsa_loss_elementwise_none_fwd(const void* pred, int dtype, const float* tar
 int nmsa_loss_elementwise_none_bwd(const void* pred, int dtype, const float* target, int64_t n,
                                    int kind, int upstream_dtype, const void* upstream,
                                    void* grad_pred, nmsa_stream_t stream);
+/* a NaN cosine stays NaN under label -1 too (clamp_min as ATen's, no fmaxf); a poisoned row touches its own loss and gradient row only */
 int nmsa_loss_cos_rows_fwd(const void* input, int dtype, const float* target, const float* labels,
                            int64_t n_rows, int D, float margin, float* loss_rows,
                            nmsa_stream_t stream);
@@ -786,6 +794,7 @@ typedef struct nmsa_loss_item {
     void* grad;
 } nmsa_loss_item;
 size_t nmsa_multitask_loss_workspace_bytes(const nmsa_loss_item* items_host, int n_items);
+/* a NaN / infinity in an item of one total leaves every sum, loss and gradient of the other totals bit-equal, and no NaN in the spec records */
 int nmsa_multitask_loss_fwd_grad(const nmsa_loss_item* items_host, int n_items, int n_totals,
                                  int32_t* spec, float* expect, double* loss_sums, int64_t* counts,
                                  double* aux, float* out_f32, int32_t* status, void* workspace,
@@ -1059,6 +1068,7 @@ int nmsa_batch_augment(void* staging_host, void* staging_device, int n_desc, int
  *   NMSA_ERR_UNSUPPORTED for any other logits_dtype or (with labels) label_dtype.
  * ------------------------------------------------------------------------- */
 #define NMSA_SCENE_MAX_CLASSES 4096
+/* a row holding a NaN or a +inf, or all -inf: score NaN, idx 0 (softmax -> max), confusion-matrix column 0; its gradient row is NaN, also when void */
 int nmsa_scene_step(const void* logits, int logits_dtype, const void* labels, int label_dtype,
                     int B, int C, const float* class_weights, float label_smoothing,
                     float* score, int64_t* idx, float* loss, void* grad, int64_t* confmat,

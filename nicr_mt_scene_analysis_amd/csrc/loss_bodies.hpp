@@ -95,7 +95,7 @@ __device__ __forceinline__ void block_partial(double sum, double aux, long long 
 //
 // PXT pixels per lane: 4 for f32, 8 for bf16 / f16 — always 16-B loads.  The class loop
 // works in groups of U planes: group maximum with v_max3, ONE rescale of the running sum
-// per group, then 3 VALU per element (fma into the base-2 domain, v_exp_f32, add).  The
+// per group, then 4 VALU per element (x - max, times log2(e), v_exp_f32, add).  The
 // target logit x_t is fetched with one gather per pixel after the loop (the tile was just
 // streamed, the gather hits L2) instead of a compare/select per class.
 // =================================================================================
@@ -185,11 +185,13 @@ __device__ __forceinline__ void ce_scan(const void* logits, size_t img, int P, i
 #pragma unroll
             for (int u = 1; u < U; ++u) g = fmaxf(g, v[u][j]);       // (the compiler folds these into v_max3_f32)
             const float mn = fmaxf(m[j], g);
-            const float k = -mn * LOG2E;
-            float acc = s[j] * __builtin_amdgcn_exp2f(fmaf(m[j], LOG2E, k));        // rescale once per group
+            // exponents as (x - max) * log2(e): the difference first.  fma(x, log2(e), -max * log2(e)) keeps
+            // the rounding residual of max * log2(e), half an ulp of 1.44 |max|: 5e-4 at 1e4, beyond the
+            // exponent range at 1e30 (the sum became 0 or inf)
+            float acc = s[j] * __builtin_amdgcn_exp2f((m[j] - mn) * LOG2E);         // rescale once per group
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                acc += __builtin_amdgcn_exp2f(fmaf(v[u][j], LOG2E, k));
+                acc += __builtin_amdgcn_exp2f((v[u][j] - mn) * LOG2E);
                 if (SMOOTH) swx[j] = fmaf(s_w[c + u], v[u][j], swx[j]);
                 if (TRACK_T) xt[j] = (tj == u) ? v[u][j] : xt[j];
             }
@@ -202,8 +204,7 @@ __device__ __forceinline__ void ce_scan(const void* logits, size_t img, int P, i
 #pragma unroll
         for (int j = 0; j < PXT; ++j) {
             const float mn = fmaxf(m[j], v[j]);
-            const float k = -mn * LOG2E;
-            s[j] = s[j] * __builtin_amdgcn_exp2f(fmaf(m[j], LOG2E, k)) + __builtin_amdgcn_exp2f(fmaf(v[j], LOG2E, k));
+            s[j] = s[j] * __builtin_amdgcn_exp2f((m[j] - mn) * LOG2E) + __builtin_amdgcn_exp2f((v[j] - mn) * LOG2E);
             m[j] = mn;
             if (SMOOTH) swx[j] = fmaf(s_w[c], v[j], swx[j]);
             if (TRACK_T) xt[j] = (t[j] == c) ? v[j] : xt[j];
@@ -224,7 +225,7 @@ __device__ __forceinline__ void ce_fwd_body(
     const void* __restrict__ logits, const uint8_t* __restrict__ target,
     const float* __restrict__ weights, int C, int P, float ls, int vec,
     LossPartial* __restrict__ slot, int* __restrict__ status, float* __restrict__ lse2_out,
-    float* s_w, int bx, int nbx, int b, int wide = 0)
+    float* s_w, int bx, int nbx, int b, int wide = 0, size_t lse_plane = 0)
 {
     for (int c = threadIdx.x; c < C; c += LOSS_THREADS) s_w[c] = weights ? weights[c] : 1.0f;
     __syncthreads();
@@ -244,18 +245,21 @@ __device__ __forceinline__ void ce_fwd_body(
         ce_scan<DTYPE, PXT, U, SMOOTH, true, true>(logits, img, P, p0, nvalid, vec, C, s_w, tt,
                                                    m, s, swx, xts);
         if (lse2_out) {
-            // log2-domain log-sum-exp per pixel, kept for the backward pass (one read of the
-            // logits there instead of two)
+            // the column maximum and log2 of the sum of exponentials per pixel, kept for the backward pass
+            // (one read of the logits there instead of two) as two planes of `lse_plane` floats: one float
+            // max * log2(e) + log2(sum) would round to an ulp of 1.44 |max|
             float k0[PXT];
 #pragma unroll
-            for (int j = 0; j < PXT; ++j) k0[j] = -(fmaf(m[j], LOG2E, __log2f(s[j])));
+            for (int j = 0; j < PXT; ++j) k0[j] = __log2f(s[j]);
             float* q = lse2_out + (size_t)b * P + p0;
             if (vec && nvalid == PXT) {
 #pragma unroll
-                for (int j = 0; j < PXT; j += 4)
-                    *(float4*)(q + j) = make_float4(k0[j], k0[j + 1], k0[j + 2], k0[j + 3]);
+                for (int j = 0; j < PXT; j += 4) {
+                    *(float4*)(q + j) = make_float4(m[j], m[j + 1], m[j + 2], m[j + 3]);
+                    *(float4*)(q + lse_plane + j) = make_float4(k0[j], k0[j + 1], k0[j + 2], k0[j + 3]);
+                }
             } else {
-                for (int j = 0; j < nvalid; ++j) q[j] = k0[j];
+                for (int j = 0; j < nvalid; ++j) { q[j] = m[j]; q[lse_plane + j] = k0[j]; }
             }
         }
         float part = 0.f, partw = 0.f;
@@ -344,15 +348,15 @@ __device__ __forceinline__ void pack_exps(u32x2_s& r, const float* e)
         r.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(b, f16x2_s));
     }
 }
-// e of pixel j; k0 = -max log2e (only the f16 tile, which still holds the logit, needs it)
+// e of pixel j; mx = the column maximum (only the f16 tile, which still holds the logit, needs it)
 template <int DTYPE>
-__device__ __forceinline__ float exp_px(const u32x2_s r, int j, float k0)
+__device__ __forceinline__ float exp_px(const u32x2_s r, int j, float mx)
 {
     if (DTYPE == NMSA_F32) return __uint_as_float(j == 0 ? r.x : r.y);
     const f16x2_s h = __builtin_bit_cast(f16x2_s, (j < 2) ? r.x : r.y);
     const float v = (float)((j & 1) ? h.y : h.x);
     if (DTYPE == NMSA_BF16) return v;
-    return __builtin_amdgcn_exp2f(fmaf(v, LOG2E, k0));
+    return __builtin_amdgcn_exp2f((v - mx) * LOG2E);
 }
 
 template <int DTYPE>
@@ -439,7 +443,7 @@ __device__ __forceinline__ void ce_fused_body(
 #pragma unroll
         for (int j = 0; j < PXT; ++j)
             t[j] = (j < nvalid) ? (int)target[(size_t)b * P + p0 + j] - 1 : -1;       // ce.py:46
-        float m[PXT], s[PXT], swx[PXT], xt[PXT], k0[PXT];
+        float m[PXT], s[PXT], swx[PXT], xt[PXT];
 #pragma unroll
         for (int j = 0; j < PXT; ++j) { m[j] = -INFINITY; s[j] = 0.f; swx[j] = 0.f; xt[j] = 0.f; }
         int C1 = C;
@@ -451,8 +455,7 @@ __device__ __forceinline__ void ce_fused_body(
                 for (int j = 0; j < PXT; ++j) m[j] = vmax(m[j], plane_px<DTYPE>(r[c], j));
             }
         }
-#pragma unroll
-        for (int j = 0; j < PXT; ++j) k0[j] = -m[j] * LOG2E;
+        // (exponents as (x - max) * log2(e), the difference first: see ce_scan)
         if (DTYPE != NMSA_F32) keep_packed(r);
         int C2 = C, C3 = C;
         asm volatile("" : "+s"(C2));
@@ -463,7 +466,7 @@ __device__ __forceinline__ void ce_fused_body(
 #pragma unroll
                     for (int j = 0; j < PXT; ++j) {
                         const float x = plane_px<DTYPE>(r[c], j);
-                        s[j] += __builtin_amdgcn_exp2f(fmaf(x, LOG2E, k0[j]));
+                        s[j] += __builtin_amdgcn_exp2f((x - m[j]) * LOG2E);
                         if (SMOOTH) swx[j] = fmaf(s_w[c], x, swx[j]);
                         xt[j] = (t[j] == c) ? x : xt[j];                   // forward only: no third walk
                     }
@@ -473,9 +476,6 @@ __device__ __forceinline__ void ce_fused_body(
             // sum of exp2; the exponentials take the logits' place in the tile (pack_exps; bf16
             // tiles: scaled by 2^14 through the exponent offset, see pack_exps)
             constexpr bool SHIFTED = DTYPE == NMSA_BF16;
-            float k0s[PXT];
-#pragma unroll
-            for (int j = 0; j < PXT; ++j) k0s[j] = SHIFTED ? k0[j] + CE_EXP_SHIFT : k0[j];
 #pragma unroll
             for (int c = 0; c < NP; ++c) {
                 if (c < C2) {
@@ -483,7 +483,8 @@ __device__ __forceinline__ void ce_fused_body(
 #pragma unroll
                     for (int j = 0; j < PXT; ++j) {
                         const float x = plane_px<DTYPE>(r[c], j);
-                        e[j] = __builtin_amdgcn_exp2f(fmaf(x, LOG2E, k0s[j]));
+                        e[j] = SHIFTED ? __builtin_amdgcn_exp2f(fmaf(x - m[j], LOG2E, CE_EXP_SHIFT))
+                                       : __builtin_amdgcn_exp2f((x - m[j]) * LOG2E);
                         s[j] += e[j];
                         if (SMOOTH) swx[j] = fmaf(s_w[c], x, swx[j]);
                         xt[j] = (t[j] == c) ? x : xt[j];
@@ -497,14 +498,14 @@ __device__ __forceinline__ void ce_fused_body(
 #pragma unroll
             for (int j = 0; j < PXT; ++j) {
                 if (SHIFTED) s[j] *= 0x1p-14f;                             // exact: s >= 1
-                const float k1 = -(fmaf(m[j], LOG2E, __log2f(s[j])));      // p = 2^(x log2e + k1)
+                const float k1 = -__log2f(s[j]);                           // p = 2^((x - max) log2e + k1)
                 const bool on = t[j] >= 0 && t[j] < C;
                 const float a = on ? (1.0f - ls) * s_w[t[j]] : 0.f;
                 const float ag = g * a;
                 const float abg = on ? g * (a + (SMOOTH ? (ls / C) * wsum : 0.f)) : 0.f;
                 smooth_on[j] = SMOOTH && abg != 0.f;
                 abgs[j] = SHIFTED ? (abg / s[j]) * 0x1p-14f : abg / s[j];  // the tile holds e * 2^14
-                const float pt = __builtin_amdgcn_exp2f(fmaf(xt[j], LOG2E, k1));
+                const float pt = __builtin_amdgcn_exp2f(fmaf(xt[j] - m[j], LOG2E, k1));
                 qt[j] = fmaf(abg, pt, smooth_on[j] ? -(g * (ls / C) * s_w[on ? t[j] : 0]) : 0.f) - ag;
             }
             if (DTYPE != NMSA_F32) keep_packed(r);
@@ -516,7 +517,7 @@ __device__ __forceinline__ void ce_fused_body(
                     const float bjg = SMOOTH ? g * (ls / C) * s_w[c] : 0.f;
 #pragma unroll
                     for (int j = 0; j < PXT; ++j) {
-                        const float q = fmaf(abgs[j], exp_px<DTYPE>(r[c], j, k0[j]), smooth_on[j] ? -bjg : 0.f);
+                        const float q = fmaf(abgs[j], exp_px<DTYPE>(r[c], j, m[j]), smooth_on[j] ? -bjg : 0.f);
                         o[j] = (t[j] == c) ? qt[j] : q;
                     }
                     if (write_grad) st_plane8<DTYPE>(grad, img + (size_t)c * P + p0, nvalid, vec, o);
@@ -554,14 +555,19 @@ __device__ __forceinline__ void ce_fused_body(
 // pixels contribute nothing and the count is the number of positive (target == 1) masked pixels.
 __device__ __forceinline__ float focal_value(float x, float y)
 {
-    const float p = fminf(fmaxf(x, 1e-4f), 1.0f - 1e-4f);
+    // torch.clamp: comparisons and selects, so a NaN prediction stays one (fmaxf(NaN, lo) is lo and
+    // would hide it in a finite loss); +-inf are clamped like every other value
+    const float lo = 1e-4f, hi = 1.0f - 1e-4f;
+    const float p = (x < lo) ? lo : (x > hi) ? hi : x;
     if (y == 1.0f) return -(1.0f - p) * (1.0f - p) * __logf(p);
     const float w = (1.0f - y) * (1.0f - y);
     return -w * w * p * p * __logf(1.0f - p);
 }
 __device__ __forceinline__ float focal_grad(float x, float y)
 {
-    if (!(x > 1e-4f && x < 1.0f - 1e-4f)) return 0.f;     // clamped: no gradient
+    // clamped: no gradient; a NaN too (the backward of torch.clamp selects on (x >= lo) & (x <= hi),
+    // false for a NaN: the poison shows in the loss, the gradient of that element is 0)
+    if (!(x > 1e-4f && x < 1.0f - 1e-4f)) return 0.f;
     const float q = 1.0f - x;
     if (y == 1.0f) return 2.0f * q * __logf(x) - q * q / x;
     const float w = (1.0f - y) * (1.0f - y);

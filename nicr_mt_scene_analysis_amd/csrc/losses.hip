@@ -67,7 +67,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_ce_fwd(
     extern __shared__ float s_w[];
     ce_fwd_body<DTYPE, PXT, SMOOTH, U>(logits, target, weights, C, P, ls, vec,
                                        partials + (size_t)blockIdx.y * gridDim.x + blockIdx.x, status,
-                                       lse2_out, s_w, blockIdx.x, gridDim.x, blockIdx.y, wide);
+                                       lse2_out, s_w, blockIdx.x, gridDim.x, blockIdx.y, wide,
+                                       (size_t)gridDim.y * P);
 }
 
 // d loss_sum / d logits, times the upstream gradient *gscale  (ce.py via autograd)
@@ -110,25 +111,28 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_ce_bwd(
             t[j] = (j < nvalid) ? ce_label(target, wide, (size_t)b * P + p0 + j) - 1 : -1;
         float ag[PXT], abg[PXT], k0[PXT];
         if (lse2) {
-            // the forward pass left -log2(sum exp) per pixel: no first pass over the logits
+            // the forward pass left the column maximum and log2(sum exp) per pixel (two planes): no first
+            // pass over the logits
+            const size_t lse_plane = (size_t)gridDim.y * P;
 #pragma unroll
-            for (int j = 0; j < PXT; ++j) k0[j] = 0.f;
+            for (int j = 0; j < PXT; ++j) { k0[j] = 0.f; m[j] = 0.f; }
             const float* q = lse2 + (size_t)b * P + p0;
             if (vec && nvalid == PXT) {
 #pragma unroll
                 for (int j = 0; j < PXT; j += 4) {
-                    const float4 f = *(const float4*)(q + j);
-                    k0[j] = f.x; k0[j + 1] = f.y; k0[j + 2] = f.z; k0[j + 3] = f.w;
+                    const float4 f = *(const float4*)(q + j), h = *(const float4*)(q + lse_plane + j);
+                    m[j] = f.x; m[j + 1] = f.y; m[j + 2] = f.z; m[j + 3] = f.w;
+                    k0[j] = -h.x; k0[j + 1] = -h.y; k0[j + 2] = -h.z; k0[j + 3] = -h.w;
                 }
             } else {
-                for (int j = 0; j < nvalid; ++j) k0[j] = q[j];
+                for (int j = 0; j < nvalid; ++j) { m[j] = q[j]; k0[j] = -q[lse_plane + j]; }
             }
         } else {
             // pass 1 with regular loads (the tile may still be in L2 / MALL for pass 2)
             ce_scan<DTYPE, PXT, U, LOSS && SMOOTH, LOSS, false>(logits, img, P, p0, nvalid, vec, C,
                                                                 s_w, t, m, s, swx, xts);
 #pragma unroll
-            for (int j = 0; j < PXT; ++j) k0[j] = -(fmaf(m[j], LOG2E, __log2f(s[j])));
+            for (int j = 0; j < PXT; ++j) k0[j] = -__log2f(s[j]);         // p = 2^((x - max) log2e + k0)
             if (LOSS) {
                 float part = 0.f, partw = 0.f;
 #pragma unroll
@@ -158,7 +162,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_ce_bwd(
             const float bjg = SMOOTH ? g * (ls / C) * s_w[c] : 0.f;
 #pragma unroll
             for (int j = 0; j < PXT; ++j) {
-                const float pj = __builtin_amdgcn_exp2f(fmaf(v[j], LOG2E, k0[j]));
+                const float pj = __builtin_amdgcn_exp2f(fmaf(v[j] - m[j], LOG2E, k0[j]));
                 float r = fmaf(abg[j], pj, (SMOOTH && abg[j] != 0.f) ? -bjg : 0.f);
                 r -= (t[j] == c) ? ag[j] : 0.f;
                 o[j] = r;
@@ -646,8 +650,8 @@ __global__ __launch_bounds__(COS_THREADS) void k_cos_emb_lds(
                     for (int u = 0; u < U; ++u) {
                         float o[PXT];
 #pragma unroll
-                        for (int j = 0; j < PXT; ++j)
-                            o[j] = fmaf(k2[j], v[u][j], k1[j] * s_lut[row[j] + d + u]);
+                        for (int j = 0; j < PXT; ++j)       // (a select: 0 * NaN of a pixel without target is NaN)
+                            o[j] = on[j] ? fmaf(k2[j], v[u][j], k1[j] * s_lut[row[j] + d + u]) : 0.f;
                         stpx<DTYPE, PXT, GRAD_NT>(grad, base + (size_t)(d + u) * P, nvalid, vec, o);
                     }
                 }
@@ -655,7 +659,7 @@ __global__ __launch_bounds__(COS_THREADS) void k_cos_emb_lds(
                     float v[PXT], o[PXT];
                     ldpx<DTYPE, PXT, true>(pred, base + (size_t)d * P, nvalid, vec, v);
 #pragma unroll
-                    for (int j = 0; j < PXT; ++j) o[j] = fmaf(k2[j], v[j], k1[j] * s_lut[row[j] + d]);
+                    for (int j = 0; j < PXT; ++j) o[j] = on[j] ? fmaf(k2[j], v[j], k1[j] * s_lut[row[j] + d]) : 0.f;
                     stpx<DTYPE, PXT, GRAD_NT>(grad, base + (size_t)d * P, nvalid, vec, o);
                 }
             }

@@ -73,7 +73,9 @@ __global__ __launch_bounds__(256) void k_cos_rows(
         const float c = xy / den;
         const float lab = labels ? labels[r] : 1.0f;
         if (!BWD) {
-            if (lane == 0) loss_rows[r] = lab == 1.0f ? 1.0f - c : (lab == -1.0f ? fmaxf(c - margin, 0.f) : 0.f);
+            // clamp_min as ATen's: a select, so a NaN cosine stays one (fmaxf(NaN, 0) is 0)
+            const float v = c - margin;
+            if (lane == 0) loss_rows[r] = lab == 1.0f ? 1.0f - c : (lab == -1.0f ? (v < 0.f ? 0.f : v) : 0.f);
         } else {
             // d cos / d x = y / den - cos * x / (|x|^2 + eps)
             const float s = lab == 1.0f ? -1.0f : ((lab == -1.0f && c - margin >= 0.f) ? 1.0f : 0.f);

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(LOSS_THREADS) __attribute__((amdgpu_waves_per_eu(NG
     }
     const uint64_t present = ((uint64_t)(NP > 32 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)phi) : 0u) << 32) |
                              (uint32_t)__builtin_amdgcn_readfirstlane((int)plo);
-    float m[PXT], s[PXT], swx[PXT], xt[PXT], k0[PXT];
+    float m[PXT], s[PXT], swx[PXT], xt[PXT];
 #pragma unroll
     for (int j = 0; j < PXT; ++j) { m[j] = -INFINITY; s[j] = 0.f; swx[j] = 0.f; xt[j] = 0.f; }
     {
@@ -194,15 +194,12 @@ __global__ __launch_bounds__(LOSS_THREADS) __attribute__((amdgpu_waves_per_eu(NG
 #pragma unroll
     for (int j = 0; j < PXT; ++j) s_m[w * TPX + l * PXT + j] = m[j];
     if (!(NMSA_CE_ABL & 2)) __syncthreads();           // (also: the last tile's sums have been read)
-    float k0s[PXT];
 #pragma unroll
     for (int j = 0; j < PXT; ++j) {
         float mm = s_m[l * PXT + j];
 #pragma unroll
         for (int ww = 1; ww < NWV; ++ww) mm = vmax(mm, s_m[ww * TPX + l * PXT + j]);
-        m[j] = mm;
-        k0[j] = -mm * LOG2E;
-        k0s[j] = SHIFTED ? k0[j] + CE_EXP_SHIFT : k0[j];
+        m[j] = mm;                                     // (exponents as (x - max) * log2(e): see ce_scan)
     }
     if (DTYPE != NMSA_F32) keep_packed(r);
     // ---- sum of exp2; MODE 0 / 2: the exponentials take the logits' place in the tile ---------------
@@ -216,7 +213,8 @@ __global__ __launch_bounds__(LOSS_THREADS) __attribute__((amdgpu_waves_per_eu(NG
 #pragma unroll
             for (int j = 0; j < PXT; ++j) {
                 const float x = plane_px<DTYPE>(r[i], j);
-                e[j] = (NMSA_CE_ABL & 1) ? fmaf(x, LOG2E, k0s[j]) : __builtin_amdgcn_exp2f(fmaf(x, LOG2E, k0s[j]));
+                const float arg = SHIFTED ? fmaf(x - m[j], LOG2E, CE_EXP_SHIFT) : (x - m[j]) * LOG2E;
+                e[j] = (NMSA_CE_ABL & 1) ? arg : __builtin_amdgcn_exp2f(arg);
                 s[j] += e[j];
                 if (SMOOTH) swx[j] = fmaf(wc, x, swx[j]);
             }
@@ -246,7 +244,7 @@ __global__ __launch_bounds__(LOSS_THREADS) __attribute__((amdgpu_waves_per_eu(NG
         }
         if (SHIFTED) ss *= 0x1p-14f;                                       // exact: the sum is >= 2^14
         s[j] = ss; swx[j] = sx;
-        const float k1 = -(fmaf(m[j], LOG2E, __log2f(ss)));                // p = 2^(x log2e + k1)
+        const float k1 = -__log2f(ss);                                     // p = 2^((x - max) log2e + k1)
         const bool on = t[j] >= 0 && t[j] < C;
         const float a = on ? (1.0f - ls) * s_w[t[j]] : 0.f;
         const float ag = g * a;
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(LOSS_THREADS) __attribute__((amdgpu_waves_per_eu(NG
         abgs[j] = SHIFTED ? (abg / ss) * 0x1p-14f : abg / ss;              // the tile holds e (* 2^14)
         // the target class, where p - 1 would cancel, from its logit (only the wave that holds it
         // has the logit; the others never select this value)
-        const float pt = __builtin_amdgcn_exp2f(fmaf(xt[j], LOG2E, k1));
+        const float pt = __builtin_amdgcn_exp2f(fmaf(xt[j] - m[j], LOG2E, k1));
         qt[j] = fmaf(abg, pt, smooth_on[j] ? -(g * (ls / C) * s_w[on ? t[j] : 0]) : 0.f) - ag;
     }
     if (MODE != 1) {
@@ -272,7 +270,7 @@ __global__ __launch_bounds__(LOSS_THREADS) __attribute__((amdgpu_waves_per_eu(NG
                 const float bjg = SMOOTH ? g * (ls / C) * s_w[c] : 0.f;
 #pragma unroll
                 for (int j = 0; j < PXT; ++j)
-                    o[j] = fmaf(abgs[j], exp_px<DTYPE>(r[i], j, k0[j]), smooth_on[j] ? -bjg : 0.f);
+                    o[j] = fmaf(abgs[j], exp_px<DTYPE>(r[i], j, m[j]), smooth_on[j] ? -bjg : 0.f);
                 if (hits) {
 #pragma unroll
                     for (int j = 0; j < PXT; ++j) o[j] = (t[j] == c) ? qt[j] : o[j];

@@ -163,6 +163,12 @@ __global__ __launch_bounds__(SC_THREADS) void k_scene_step(SceneArgs a)
                 if (eps > 0.0) wx += (a.weights ? (double)a.weights[c] : 1.0) * x;
             }
             s = wave_allreduce_sum(s);
+            // a row that holds a NaN or a +inf, or is all -inf: its softmax is all NaN (exp(x - m) has
+            // a NaN term exactly then; every other row sums terms in [0, 1] with one of them 1), and
+            // torch.max of an all-NaN row answers its first element: score NaN, index 0.  The argmax
+            // of the raw logits above would drop a NaN and follow a +inf.
+            const bool poisoned = s != s;
+            if (poisoned) bi = 0;
 
             long long l = 0;
             if (a.labels) l = ld_label(a.labels, a.label_dtype, r);
@@ -189,7 +195,9 @@ __global__ __launch_bounds__(SC_THREADS) void k_scene_step(SceneArgs a)
             }
             if (want_grad) {
                 for (int c = lane; c < C; c += kWave) {
-                    double g = 0.0;
+                    // a void row: 0, but NaN where its softmax is (F.cross_entropy hands an ignored row
+                    // 0 - softmax * 0 through log_softmax's backward)
+                    double g = poisoned ? (double)NAN : 0.0;
                     if (valid) {
                         const double x = (double)ld_logit<DTYPE>(a.logits, base + c);
                         const double p = exp(x - m) / s;

@@ -214,9 +214,9 @@ class CrossEntropyFunction(torch.autograd.Function):
                 L.ptr(exp), L.ptr(s), L.ptr(n), L.ptr(wsum), L.ptr(grad), L.ptr(status),
                 L.ptr(ws), nbytes, L.stream_ptr(dev)), 'nmsa_loss_ce_fwd_grad')
         else:
-            # per-pixel log-sum-exp for the backward pass (4 B/px instead of a second read of
-            # the logits), only when a gradient can be asked for
-            lse2 = torch.empty((B, H, W), dtype=torch.float32, device=dev) \
+            # per-pixel column maximum and log2 of the sum of exponentials for the backward pass (two
+            # planes, 8 B/px instead of a second read of the logits), only when a gradient can be asked for
+            lse2 = torch.empty((2, B, H, W), dtype=torch.float32, device=dev) \
                 if ctx.needs_input_grad[0] else None
             fwd = L.lib().nmsa_loss_ce_fwd_i16 if wide else L.lib().nmsa_loss_ce_fwd
             L.check(fwd(
