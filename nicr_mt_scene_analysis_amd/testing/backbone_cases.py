@@ -108,11 +108,13 @@ def package_namespace() -> SimpleNamespace:
                            get_encoder_fusion_class=model.get_encoder_fusion_class)
 
 
-def _backbone(ns, block: str, se: bool, d16: bool, channels: int):
+def _backbone(ns, block: str, se: bool, d16: bool, channels: int, activation=None, dropout_p: float = 0.0):
+    """`activation` (a class; default: the package's) and `dropout_p` are for testing/network_cases.py"""
     cls = ns.ResNetSEBackbone if se else ns.ResNetBackbone
-    kwargs = {'dropout_p': 0.0} if block == 'nonbottleneck1d' else {}      # no random draw in the records
+    kwargs = {'dropout_p': dropout_p} if block == 'nonbottleneck1d' else {}     # 0: no random draw in the records
+    extra = {} if activation is None else {'activation': activation}
     return cls(block=ns.get_block_class(block, **kwargs), layers=list(LAYERS), n_input_channels=channels,
-               replace_stride_with_dilation=[False, False, True] if d16 else None)
+               replace_stride_with_dilation=[False, False, True] if d16 else None, **extra)
 
 
 def build(config: str, ns=None):
