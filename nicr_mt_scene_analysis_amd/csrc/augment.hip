@@ -45,11 +45,6 @@ constexpr int AUG_DESC_WORDS = 24;
 
 static_assert(sizeof(nmsa_augment_desc) == AUG_DESC_WORDS * 4, "the staging layout is 24 words per descriptor");
 
-template <typename T, int N>
-struct alignas(sizeof(T) * N > 16 ? 16 : sizeof(T) * N) pack {
-    T v[N];
-};
-
 struct op_move {
     template <typename T>
     __device__ __forceinline__ T operator()(T v, int) const { return v; }

@@ -25,7 +25,7 @@
 // Grids: min(items, BNT_BLOCKS_PER_CU per compute unit of nmsa_device_geometry) workgroups of four waves,
 // looping over the rest; an item is four consecutive units (a channel when the reduce finishes alone).
 // Addressing: 32-bit, B*C*H*W < 2^31 is checked.  The arithmetic contract is stated in include/nmsa.h.
-#include "loss_common.hpp"
+#include "nmsa_common.hpp"
 #include <math.h>
 
 namespace nmsa {
@@ -36,26 +36,7 @@ constexpr int BNT_WAVES = BNT_THREADS / kWave;
 constexpr int BNT_SEG = NMSA_BNTAIL_SEGMENT;
 constexpr int BNT_BLOCKS_PER_CU = 8;
 
-template <int DTYPE> struct bnt_elem { typedef uint16_t type; };
-template <> struct bnt_elem<NMSA_F32> { typedef float type; };
-
-template <int DTYPE>
-__device__ __forceinline__ float bnt_ld(typename bnt_elem<DTYPE>::type v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
-    else return f16_to_f32(v);
-}
-
-template <int DTYPE>
-__device__ __forceinline__ typename bnt_elem<DTYPE>::type bnt_st(float v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
-    else return f32_to_f16(v);
-}
-
-template <typename S, int VEC> struct alignas(sizeof(S) * VEC) bnt_pack { S v[VEC]; };
+// elem, ld, st, pack: nmsa_common.hpp
 
 __device__ __forceinline__ float bnt_sigmoid(float z)
 {
@@ -79,34 +60,34 @@ __device__ __forceinline__ float bnt_silu_grad(float z)
 // V elements of a plane of HW elements from element e as float32; ELEMENT route: what lies behind the
 // plane is +0.  The caller has checked e < HW.
 template <int DTYPE, bool VECTOR>
-__device__ __forceinline__ void bnt_load(const typename bnt_elem<DTYPE>::type* plane, uint32_t e, uint32_t HW, float* out)
+__device__ __forceinline__ void bnt_load(const typename elem<DTYPE>::type* plane, uint32_t e, uint32_t HW, float* out)
 {
-    typedef typename bnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     if constexpr (VECTOR) {
-        const bnt_pack<S, V> p = *(const bnt_pack<S, V>*)(plane + e);
+        const pack<S, V> p = *(const pack<S, V>*)(plane + e);
 #pragma unroll
-        for (int j = 0; j < V; ++j) out[j] = bnt_ld<DTYPE>(p.v[j]);
+        for (int j = 0; j < V; ++j) out[j] = ld<DTYPE>(p.v[j]);
     } else {
 #pragma unroll
-        for (int j = 0; j < V; ++j) out[j] = e + j < HW ? bnt_ld<DTYPE>(plane[e + j]) : 0.0f;
+        for (int j = 0; j < V; ++j) out[j] = e + j < HW ? ld<DTYPE>(plane[e + j]) : 0.0f;
     }
 }
 
 template <int DTYPE, bool VECTOR>
-__device__ __forceinline__ void bnt_store(typename bnt_elem<DTYPE>::type* plane, uint32_t e, uint32_t HW, const float* in)
+__device__ __forceinline__ void bnt_store(typename elem<DTYPE>::type* plane, uint32_t e, uint32_t HW, const float* in)
 {
-    typedef typename bnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     if constexpr (VECTOR) {
-        bnt_pack<S, V> p;
+        pack<S, V> p;
 #pragma unroll
-        for (int j = 0; j < V; ++j) p.v[j] = bnt_st<DTYPE>(in[j]);
-        *(bnt_pack<S, V>*)(plane + e) = p;
+        for (int j = 0; j < V; ++j) p.v[j] = st<DTYPE>(in[j]);
+        *(pack<S, V>*)(plane + e) = p;
     } else {
 #pragma unroll
         for (int j = 0; j < V; ++j)
-            if (e + j < HW) plane[e + j] = bnt_st<DTYPE>(in[j]);
+            if (e + j < HW) plane[e + j] = st<DTYPE>(in[j]);
     }
 }
 
@@ -190,10 +171,10 @@ __device__ __forceinline__ void bnt_merge_sums(const float* part_c, uint32_t U, 
 // M2_u = sum (x - mean_u)^2 as fused multiply-adds from 0 in the same order
 template <int DTYPE, bool VECTOR>
 __global__ __launch_bounds__(BNT_THREADS) void k_bntail_stats(
-    const typename bnt_elem<DTYPE>::type* __restrict__ x, float* __restrict__ part, const uint32_t HW,
+    const typename elem<DTYPE>::type* __restrict__ x, float* __restrict__ part, const uint32_t HW,
     const uint32_t C, const uint32_t nseg, const uint32_t U, const uint32_t units, const uint32_t items)
 {
-    typedef typename bnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     constexpr int KCH = BNT_SEG / (kWave * V);
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
@@ -259,12 +240,12 @@ struct BntFwdArgs {
 // IEEE square root and division
 template <int DTYPE, bool VECTOR, int ACT>
 __global__ __launch_bounds__(BNT_THREADS) void k_bntail_apply(
-    const typename bnt_elem<DTYPE>::type* __restrict__ x, const typename bnt_elem<DTYPE>::type* __restrict__ identity,
-    const typename bnt_elem<DTYPE>::type* __restrict__ scale, const BntFwdArgs p,
-    typename bnt_elem<DTYPE>::type* __restrict__ y, const uint32_t HW, const uint32_t C, const uint32_t nseg,
+    const typename elem<DTYPE>::type* __restrict__ x, const typename elem<DTYPE>::type* __restrict__ identity,
+    const typename elem<DTYPE>::type* __restrict__ scale, const BntFwdArgs p,
+    typename elem<DTYPE>::type* __restrict__ y, const uint32_t HW, const uint32_t C, const uint32_t nseg,
     const uint32_t U, const uint32_t units, const uint32_t items)
 {
-    typedef typename bnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     constexpr int KCH = BNT_SEG / (kWave * V);
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
@@ -293,7 +274,7 @@ __global__ __launch_bounds__(BNT_THREADS) void k_bntail_apply(
             }
         }
         const float gamma = p.gamma[t.c], beta = p.beta[t.c];
-        const float sc = scale ? bnt_ld<DTYPE>(scale[t.plane]) : 1.0f;
+        const float sc = scale ? ld<DTYPE>(scale[t.plane]) : 1.0f;
         const S* xs = x + (size_t)t.plane * HW;
         const S* is = identity ? identity + (size_t)t.plane * HW : nullptr;
         S* ys = y + (size_t)t.plane * HW;
@@ -352,11 +333,11 @@ __device__ __forceinline__ void bnt_grad(const float* gy, const float* xh, const
 // sum gu * xh as fused multiply-adds), then as in bnt_wave_sum
 template <int DTYPE, bool VECTOR, int ACT>
 __device__ __forceinline__ void bnt_bwd_unit(
-    const typename bnt_elem<DTYPE>::type* gy, const typename bnt_elem<DTYPE>::type* x,
-    const typename bnt_elem<DTYPE>::type* aux, const BntUnit& t, uint32_t HW, bool has_scale, const BntChannel& ch,
+    const typename elem<DTYPE>::type* gy, const typename elem<DTYPE>::type* x,
+    const typename elem<DTYPE>::type* aux, const BntUnit& t, uint32_t HW, bool has_scale, const BntChannel& ch,
     float& sum_gu, float& sum_gux)
 {
-    typedef typename bnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     constexpr int KCH = BNT_SEG / (kWave * V);
     const S* gs = gy + (size_t)t.plane * HW;
@@ -387,7 +368,7 @@ __device__ __forceinline__ void bnt_bwd_unit(
 }
 
 template <int DTYPE>
-__device__ __forceinline__ BntChannel bnt_channel(const BntBwdArgs& p, const typename bnt_elem<DTYPE>::type* scale,
+__device__ __forceinline__ BntChannel bnt_channel(const BntBwdArgs& p, const typename elem<DTYPE>::type* scale,
                                                   const BntUnit& t, bool silu)
 {
     BntChannel ch;
@@ -395,7 +376,7 @@ __device__ __forceinline__ BntChannel bnt_channel(const BntBwdArgs& p, const typ
     ch.invstd = p.invstd[t.c];
     ch.gamma = p.gamma[t.c];
     ch.beta = silu ? p.beta[t.c] : 0.0f;
-    ch.scale = scale ? bnt_ld<DTYPE>(scale[t.plane]) : 1.0f;
+    ch.scale = scale ? ld<DTYPE>(scale[t.plane]) : 1.0f;
     return ch;
 }
 
@@ -403,8 +384,8 @@ __device__ __forceinline__ BntChannel bnt_channel(const BntBwdArgs& p, const typ
 // workgroup owns a channel (item = channel), and wave 0 merges what the workgroup wrote
 template <int DTYPE, bool VECTOR, int ACT>
 __global__ __launch_bounds__(BNT_THREADS) void k_bntail_bwd_reduce(
-    const typename bnt_elem<DTYPE>::type* __restrict__ gy, const typename bnt_elem<DTYPE>::type* __restrict__ x,
-    const typename bnt_elem<DTYPE>::type* __restrict__ aux, const typename bnt_elem<DTYPE>::type* __restrict__ scale,
+    const typename elem<DTYPE>::type* __restrict__ gy, const typename elem<DTYPE>::type* __restrict__ x,
+    const typename elem<DTYPE>::type* __restrict__ aux, const typename elem<DTYPE>::type* __restrict__ scale,
     const BntBwdArgs p, float* part, const uint32_t HW, const uint32_t C, const uint32_t nseg, const uint32_t U,
     const uint32_t units, const uint32_t items)
 {
@@ -456,13 +437,13 @@ __global__ __launch_bounds__(BNT_THREADS) void k_bntail_bwd_reduce(
 // a NULL gx / gid is not wanted
 template <int DTYPE, bool VECTOR, int ACT>
 __global__ __launch_bounds__(BNT_THREADS) void k_bntail_bwd_apply(
-    const typename bnt_elem<DTYPE>::type* __restrict__ gy, const typename bnt_elem<DTYPE>::type* __restrict__ x,
-    const typename bnt_elem<DTYPE>::type* __restrict__ aux, const typename bnt_elem<DTYPE>::type* __restrict__ scale,
-    const BntBwdArgs p, const float* __restrict__ part, typename bnt_elem<DTYPE>::type* __restrict__ gx,
-    typename bnt_elem<DTYPE>::type* __restrict__ gid, const uint32_t HW, const uint32_t C, const uint32_t nseg,
+    const typename elem<DTYPE>::type* __restrict__ gy, const typename elem<DTYPE>::type* __restrict__ x,
+    const typename elem<DTYPE>::type* __restrict__ aux, const typename elem<DTYPE>::type* __restrict__ scale,
+    const BntBwdArgs p, const float* __restrict__ part, typename elem<DTYPE>::type* __restrict__ gx,
+    typename elem<DTYPE>::type* __restrict__ gid, const uint32_t HW, const uint32_t C, const uint32_t nseg,
     const uint32_t U, const uint32_t units, const uint32_t items)
 {
-    typedef typename bnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     constexpr int KCH = BNT_SEG / (kWave * V);
     constexpr bool SILU = ACT == NMSA_BNTAIL_ACT_SILU;
@@ -512,9 +493,7 @@ __global__ __launch_bounds__(BNT_THREADS) void k_bntail_bwd_apply(
 }
 
 // ------------------------------------------------------------------------------------ host side
-bool bnt_aligned(const void* p, int dtype) { return (uintptr_t)p % (dtype == NMSA_F32 ? 4u : 2u) == 0; }
-bool bnt_f32(const void* p) { return (uintptr_t)p % 4u == 0; }
-bool bnt_on16(const void* p) { return !p || (uintptr_t)p % 16u == 0; }
+bool bnt_f32(const void* p) { return aligned(p, 4); }
 int bnt_vec(int dtype) { return dtype == NMSA_F32 ? 4 : 8; }
 
 bool bnt_sizes_ok(int dtype, int B, int C, int H, int W)
@@ -554,14 +533,8 @@ bool bnt_vector(const void* const* maps, int n, int dtype, int64_t HW)
 {
     if (HW % bnt_vec(dtype) != 0) return false;
     for (int i = 0; i < n; ++i)
-        if (!bnt_on16(maps[i])) return false;
+        if (!aligned(maps[i], 16)) return false;
     return true;
-}
-
-unsigned bnt_grid(uint32_t items)
-{
-    const uint64_t cap = (uint64_t)device_geometry().cus * BNT_BLOCKS_PER_CU;
-    return (unsigned)(items < cap ? items : cap);
 }
 
 }  // namespace
@@ -591,7 +564,7 @@ extern "C" int nmsa_bntail_route(const void* t0, const void* t1, const void* t2,
     const void* maps[5] = {t0, t1, t2, t3, t4};
     if (!t0) return NMSA_ERR_ARG;
     for (int i = 0; i < 5; ++i)
-        if (!bnt_aligned(maps[i], dtype)) return NMSA_ERR_ARG;
+        if (!elem_aligned(maps[i], dtype)) return NMSA_ERR_ARG;
     if (segments) *segments = (int)bnt_shape(1, 1, H, W).nseg;
     return bnt_vector(maps, 5, dtype, (int64_t)H * W) ? NMSA_BNTAIL_ROUTE_VECTOR : NMSA_BNTAIL_ROUTE_ELEMENT;
 }
@@ -602,15 +575,15 @@ extern "C" int nmsa_bntail_stats(const void* x, int dtype, int B, int C, int H, 
     using namespace nmsa;
     hipStream_t stream = (hipStream_t)stream_;
     if (!bnt_sizes_ok(dtype, B, C, H, W)) return NMSA_ERR_ARG;
-    if (!x || !part || !bnt_aligned(x, dtype) || !bnt_f32(part)) return NMSA_ERR_ARG;
+    if (!x || !part || !elem_aligned(x, dtype) || !bnt_f32(part)) return NMSA_ERR_ARG;
     if (part_bytes < bnt_part_bytes(B, C, H, W)) return NMSA_ERR_ARG;
     const BntShape s = bnt_shape(B, C, H, W);
     const void* maps[1] = {x};
     const bool vector = bnt_vector(maps, 1, dtype, s.HW);
-    const dim3 grid(bnt_grid(s.items)), block(BNT_THREADS);
+    const dim3 grid(capped_grid(s.items, BNT_BLOCKS_PER_CU)), block(BNT_THREADS);
 #define BNT_STATS(DT)                                                                                            \
     do {                                                                                                         \
-        typedef bnt_elem<DT>::type S;                                                                            \
+        typedef elem<DT>::type S;                                                                                \
         if (vector)                                                                                              \
             hipLaunchKernelGGL((k_bntail_stats<DT, true>), grid, block, 0, stream, (const S*)x, part, s.HW, s.C, \
                                s.nseg, s.U, s.units, s.items);                                                   \
@@ -632,7 +605,7 @@ extern "C" int nmsa_bntail_apply(const void* x, const void* identity, const void
     hipStream_t stream = (hipStream_t)stream_;
     if (!bnt_sizes_ok(dtype, B, C, H, W) || !bnt_act_ok(act)) return NMSA_ERR_ARG;
     if (!x || !y || !gamma || !beta || !running_mean || !running_var) return NMSA_ERR_ARG;
-    if (!bnt_aligned(x, dtype) || !bnt_aligned(identity, dtype) || !bnt_aligned(scale, dtype) || !bnt_aligned(y, dtype))
+    if (!elem_aligned(x, dtype) || !elem_aligned(identity, dtype) || !elem_aligned(scale, dtype) || !elem_aligned(y, dtype))
         return NMSA_ERR_ARG;
     if (!bnt_f32(gamma) || !bnt_f32(beta) || !bnt_f32(part) || !bnt_f32(running_mean) || !bnt_f32(running_var) ||
         !bnt_f32(save_mean) || !bnt_f32(save_invstd))
@@ -646,11 +619,11 @@ extern "C" int nmsa_bntail_apply(const void* x, const void* identity, const void
     const double M = (double)B * H * W;
     const BntFwdArgs p = {gamma, beta, part, running_mean, running_var, save_mean, save_invstd,
                           eps, momentum, (float)M, (float)(M - 1.0)};
-    const dim3 grid(bnt_grid(s.items)), block(BNT_THREADS);
+    const dim3 grid(capped_grid(s.items, BNT_BLOCKS_PER_CU)), block(BNT_THREADS);
 #define BNT_APPLY_ONE(DT, VECTOR, ACT)                                                                         \
-    hipLaunchKernelGGL((k_bntail_apply<DT, VECTOR, ACT>), grid, block, 0, stream, (const bnt_elem<DT>::type*)x, \
-                       (const bnt_elem<DT>::type*)identity, (const bnt_elem<DT>::type*)scale, p,                \
-                       (bnt_elem<DT>::type*)y, s.HW, s.C, s.nseg, s.U, s.units, s.items)
+    hipLaunchKernelGGL((k_bntail_apply<DT, VECTOR, ACT>), grid, block, 0, stream, (const elem<DT>::type*)x,    \
+                       (const elem<DT>::type*)identity, (const elem<DT>::type*)scale, p,                       \
+                       (elem<DT>::type*)y, s.HW, s.C, s.nseg, s.U, s.units, s.items)
 #define BNT_APPLY(DT) BNT_DISPATCH(DT, BNT_APPLY_ONE)
     NMSA_DISPATCH_DTYPE(dtype, BNT_APPLY)
 #undef BNT_APPLY
@@ -667,7 +640,7 @@ int bnt_bwd_check(const void* gy, const void* x, const void* aux, const void* sc
     if (!bnt_sizes_ok(dtype, B, C, H, W) || !bnt_act_ok(act)) return NMSA_ERR_ARG;
     if (!gy || !x || !gamma || !mean || !invstd) return NMSA_ERR_ARG;
     if (act == NMSA_BNTAIL_ACT_RELU ? !aux : !beta) return NMSA_ERR_ARG;     // y is the gate; z needs beta
-    if (!bnt_aligned(gy, dtype) || !bnt_aligned(x, dtype) || !bnt_aligned(aux, dtype) || !bnt_aligned(scale, dtype))
+    if (!elem_aligned(gy, dtype) || !elem_aligned(x, dtype) || !elem_aligned(aux, dtype) || !elem_aligned(scale, dtype))
         return NMSA_ERR_ARG;
     if (!bnt_f32(gamma) || !bnt_f32(beta) || !bnt_f32(mean) || !bnt_f32(invstd)) return NMSA_ERR_ARG;
     return NMSA_OK;
@@ -691,10 +664,10 @@ extern "C" int nmsa_bntail_bwd_reduce(const void* gy, const void* x, const void*
     const bool vector = bnt_vector(maps, 3, dtype, s.HW);
     const BntBwdArgs p = {gamma, beta, mean, invstd, dgamma, dbeta, (float)((double)B * H * W)};
     const uint32_t items = dgamma ? s.C : s.items;
-    const dim3 grid(bnt_grid(items)), block(BNT_THREADS);
+    const dim3 grid(capped_grid(items, BNT_BLOCKS_PER_CU)), block(BNT_THREADS);
 #define BNT_REDUCE_ONE(DT, VECTOR, ACT)                                                                             \
-    hipLaunchKernelGGL((k_bntail_bwd_reduce<DT, VECTOR, ACT>), grid, block, 0, stream, (const bnt_elem<DT>::type*)gy, \
-                       (const bnt_elem<DT>::type*)x, (const bnt_elem<DT>::type*)aux, (const bnt_elem<DT>::type*)scale, \
+    hipLaunchKernelGGL((k_bntail_bwd_reduce<DT, VECTOR, ACT>), grid, block, 0, stream, (const elem<DT>::type*)gy,   \
+                       (const elem<DT>::type*)x, (const elem<DT>::type*)aux, (const elem<DT>::type*)scale,          \
                        p, part, s.HW, s.C, s.nseg, s.U, s.units, items)
 #define BNT_REDUCE(DT) BNT_DISPATCH(DT, BNT_REDUCE_ONE)
     NMSA_DISPATCH_DTYPE(dtype, BNT_REDUCE)
@@ -713,7 +686,7 @@ extern "C" int nmsa_bntail_bwd_apply(const void* gy, const void* x, const void* 
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = bnt_bwd_check(gy, x, aux, scale, dtype, B, C, H, W, gamma, beta, mean, invstd, act);
     if (rc != NMSA_OK) return rc;
-    if (!bnt_aligned(gx, dtype) || !bnt_aligned(gid, dtype) || !bnt_f32(part) || !bnt_f32(dgamma) || !bnt_f32(dbeta) ||
+    if (!elem_aligned(gx, dtype) || !elem_aligned(gid, dtype) || !bnt_f32(part) || !bnt_f32(dgamma) || !bnt_f32(dbeta) ||
         !dgamma != !dbeta)
         return NMSA_ERR_ARG;
     if (dgamma && !part) return NMSA_ERR_ARG;                       // the sums come from the partials
@@ -723,11 +696,11 @@ extern "C" int nmsa_bntail_bwd_apply(const void* gy, const void* x, const void* 
     const void* maps[5] = {gy, x, aux, gx, gid};
     const bool vector = bnt_vector(maps, 5, dtype, s.HW);
     const BntBwdArgs p = {gamma, beta, mean, invstd, dgamma, dbeta, (float)((double)B * H * W)};
-    const dim3 grid(bnt_grid(s.items)), block(BNT_THREADS);
+    const dim3 grid(capped_grid(s.items, BNT_BLOCKS_PER_CU)), block(BNT_THREADS);
 #define BNT_BAPPLY_ONE(DT, VECTOR, ACT)                                                                            \
-    hipLaunchKernelGGL((k_bntail_bwd_apply<DT, VECTOR, ACT>), grid, block, 0, stream, (const bnt_elem<DT>::type*)gy, \
-                       (const bnt_elem<DT>::type*)x, (const bnt_elem<DT>::type*)aux, (const bnt_elem<DT>::type*)scale, \
-                       p, part, (bnt_elem<DT>::type*)gx, (bnt_elem<DT>::type*)gid, s.HW, s.C, s.nseg, s.U, s.units,  \
+    hipLaunchKernelGGL((k_bntail_bwd_apply<DT, VECTOR, ACT>), grid, block, 0, stream, (const elem<DT>::type*)gy,   \
+                       (const elem<DT>::type*)x, (const elem<DT>::type*)aux, (const elem<DT>::type*)scale,         \
+                       p, part, (elem<DT>::type*)gx, (elem<DT>::type*)gid, s.HW, s.C, s.nseg, s.U, s.units,        \
                        s.items)
 #define BNT_BAPPLY(DT) BNT_DISPATCH(DT, BNT_BAPPLY_ONE)
     NMSA_DISPATCH_DTYPE(dtype, BNT_BAPPLY)

@@ -8,8 +8,8 @@
 //                     rows(i) = floor(i H / ph) .. ceil((i+1) H / ph) - 1, cols(j) alike (ATen's windows)
 //   gx[n,c,h,w]     = sum_i sum_{(a,b): h in rows(a), w in cols(b)} gp_i[n,c,a,b] / float(area(a,b))
 //   out[n, 0..C)    = x;   out[n, C + off_i + c] = resize(y_i[n,c], H x W), nearest or bilinear
-//                     (align_corners = False), ATen's float index arithmetic (nearest_src of
-//                     crop_resize.hpp; bilinear_src and the blend order of resize.hip, restated here)
+//                     (align_corners = False), ATen's float index arithmetic (nearest_src,
+//                     bilinear_src and bilerp of crop_resize.hpp, shared with resize.hip)
 //   gy_i[n,c,p,q]   = sum_{h reads p} wy(h,p) * ( sum_{w reads q} wx(w,q) * g_out[n, C+off_i+c, h, w] )
 //
 // Summation orders (fixed; no atomics; the same bits on every call and on both routes):
@@ -35,7 +35,6 @@
 // scalars does not fit the scalar registers, and an item is a walk over all H rows).
 // Addressing: 64-bit plane bases, 32-bit offsets inside a plane (H, W, ph, pw <= 32768 is checked).
 #include "crop_resize.hpp"
-#include "loss_common.hpp"
 
 namespace nmsa {
 namespace {
@@ -48,24 +47,7 @@ constexpr int PPM_LDS_ROWS = 512;        // H * pw row sums of one branch
 constexpr int PPM_CAT_RUN = 4;           // pixels per lane and item of k_ppm_upcat_fwd
 constexpr int PPM_MAX_DIM = 32768;
 
-template <int DTYPE> struct ppm_elem { typedef uint16_t type; };
-template <> struct ppm_elem<NMSA_F32> { typedef float type; };
-
-template <int DTYPE>
-__device__ __forceinline__ float ppm_ld(typename ppm_elem<DTYPE>::type v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
-    else return f16_to_f32(v);
-}
-
-template <int DTYPE>
-__device__ __forceinline__ typename ppm_elem<DTYPE>::type ppm_st(float v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
-    else return f32_to_f16(v);
-}
+// elem, ld, st: nmsa_common.hpp; nearest_src, bilinear_src, bilerp: crop_resize.hpp
 
 struct PpmDesc {
     uint32_t C, H, W, HW;
@@ -76,27 +58,6 @@ struct PpmDesc {
     int ph[NMSA_PPM_MAX_BINS], pw[NMSA_PPM_MAX_BINS], cr[NMSA_PPM_MAX_BINS];
     void* p[NMSA_PPM_MAX_BINS];
 };
-
-// ATen's bilinear source (area_pixel_compute_source_index, align_corners = False) as resize.hip
-// pins it: the same operations in the same order
-__device__ __forceinline__ void ppm_bilinear_src(float scale, int dst, int in,
-                                                 int& i0, int& i1, float& w0, float& w1)
-{
-    float s = __fmaf_rn(scale, __fadd_rn((float)dst, 0.5f), -0.5f);
-    s = (s < 0.f) ? 0.f : s;
-    i0 = min((int)s, in - 1);
-    i1 = min(i0 + 1, in - 1);
-    w1 = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
-    w0 = __fsub_rn(1.0f, w1);
-}
-
-__device__ __forceinline__ float ppm_bilerp(float a, float b, float c, float d,
-                                            float wx0, float wx1, float wy0, float wy1)
-{
-    const float t0 = __fmaf_rn(a, wx0, __fmul_rn(b, wx1));
-    const float t1 = __fmaf_rn(c, wx0, __fmul_rn(d, wx1));
-    return __fmaf_rn(t0, wy0, __fmul_rn(t1, wy1));
-}
 
 // branch `b` of the descriptor (b is uniform: three scalar selects, no indexed access to the arguments)
 __device__ __forceinline__ void ppm_pick(const PpmDesc& d, int b, int& ph, int& pw, void*& p)
@@ -120,7 +81,7 @@ __device__ __forceinline__ bool ppm_reads(int mode, float scale, int dst, int in
     }
     int i0, i1;
     float w0, w1;
-    ppm_bilinear_src(scale, dst, in, i0, i1, w0, w1);
+    bilinear_src(scale, dst, in, i0, i1, w0, w1);
     wgt = __fadd_rn(i0 == cell ? w0 : 0.0f, i1 == cell ? w1 : 0.0f);
     return i0 == cell || i1 == cell;
 }
@@ -146,9 +107,9 @@ __device__ __forceinline__ void ppm_readers(int mode, float scale, int out, int 
 // ---------------------------------------------------------------------------------- pool forward
 template <int DTYPE, bool LDS>
 __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_fwd(
-    const typename ppm_elem<DTYPE>::type* __restrict__ x, const PpmDesc d)
+    const typename elem<DTYPE>::type* __restrict__ x, const PpmDesc d)
 {
-    typedef typename ppm_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     __shared__ float s_plane[LDS ? PPM_WAVES * PPM_LDS_PLANE : 1];
     __shared__ float s_rows[LDS ? PPM_WAVES * PPM_LDS_ROWS : 1];
     const int wave = threadIdx.x / kWave, lane = lane_id();
@@ -162,7 +123,7 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_fwd(
         if constexpr (LDS) {
             float* pl = s_plane + wave * PPM_LDS_PLANE;
             if (valid)
-                for (uint32_t i = lane; i < d.HW; i += kWave) pl[i] = ppm_ld<DTYPE>(xp[i]);
+                for (uint32_t i = lane; i < d.HW; i += kWave) pl[i] = ld<DTYPE>(xp[i]);
             __syncthreads();
         }
 #pragma nounroll
@@ -190,7 +151,7 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_fwd(
                         const int kw = ppm_win_hi(j, W, pw) - ppm_win_lo(j, W, pw);
                         float s = 0.0f;
                         for (int h = h0; h < h1; ++h) s = __fadd_rn(s, rows[h * pw + j]);
-                        op[cell] = ppm_st<DTYPE>(__fdiv_rn(s, (float)((h1 - h0) * kw)));
+                        op[cell] = st<DTYPE>(__fdiv_rn(s, (float)((h1 - h0) * kw)));
                     }
                 __syncthreads();
             } else {
@@ -202,10 +163,10 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_fwd(
                         float s = 0.0f;
                         for (int h = h0; h < h1; ++h) {
                             float r = 0.0f;
-                            for (int w = w0; w < w1; ++w) r = __fadd_rn(r, ppm_ld<DTYPE>(xp[h * W + w]));
+                            for (int w = w0; w < w1; ++w) r = __fadd_rn(r, ld<DTYPE>(xp[h * W + w]));
                             s = __fadd_rn(s, r);
                         }
-                        op[cell] = ppm_st<DTYPE>(__fdiv_rn(s, (float)((h1 - h0) * (w1 - w0))));
+                        op[cell] = st<DTYPE>(__fdiv_rn(s, (float)((h1 - h0) * (w1 - w0))));
                     }
             }
         }
@@ -215,10 +176,10 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_fwd(
 // --------------------------------------------------------------------------------- pool backward
 template <int DTYPE>
 __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_bwd(
-    typename ppm_elem<DTYPE>::type* __restrict__ gx, const PpmDesc d, const uint32_t side,
+    typename elem<DTYPE>::type* __restrict__ gx, const PpmDesc d, const uint32_t side,
     const uint32_t chunks, const uint32_t items)
 {
-    typedef typename ppm_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     __shared__ int s_j0[NMSA_PPM_MAX_BINS][PPM_THREADS], s_j1[NMSA_PPM_MAX_BINS][PPM_THREADS];
     __shared__ int s_kw0[NMSA_PPM_MAX_BINS][PPM_THREADS], s_kw1[NMSA_PPM_MAX_BINS][PPM_THREADS];
     const int wave = threadIdx.x / kWave, lane = lane_id();
@@ -262,11 +223,11 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_bwd(
                     const int kh = ppm_win_hi(i, H, ph) - ppm_win_lo(i, H, ph);
                     for (int j = j0; j <= j1; ++j) {
                         const int kw = j == j0 ? kw0 : (j == j1 ? kw1 : ppm_win_hi(j, W, pw) - ppm_win_lo(j, W, pw));
-                        acc = __fadd_rn(acc, __fdiv_rn(ppm_ld<DTYPE>(src[i * pw + j]), (float)(kh * kw)));
+                        acc = __fadd_rn(acc, __fdiv_rn(ld<DTYPE>(src[i * pw + j]), (float)(kh * kw)));
                     }
                 }
             }
-            gp[h * W + w] = ppm_st<DTYPE>(acc);
+            gp[h * W + w] = st<DTYPE>(acc);
         }
     }
 }
@@ -274,10 +235,10 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_pool_bwd(
 // ------------------------------------------------------------------- upsample + concat forward
 template <int DTYPE>
 __global__ __launch_bounds__(PPM_THREADS) void k_ppm_upcat_fwd(
-    const typename ppm_elem<DTYPE>::type* __restrict__ x, typename ppm_elem<DTYPE>::type* __restrict__ out,
+    const typename elem<DTYPE>::type* __restrict__ x, typename elem<DTYPE>::type* __restrict__ out,
     const PpmDesc d, const uint32_t chunks, const uint32_t items)
 {
-    typedef typename ppm_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     const int H = (int)d.H, W = (int)d.W;
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint32_t plane = item / chunks, chunk = item - plane * chunks;
@@ -317,17 +278,17 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_upcat_fwd(
             const int h = (int)(i / d.W), w = (int)(i - (uint32_t)h * d.W);
             float v;
             if (d.mode == NMSA_PPM_NEAREST) {
-                v = ppm_ld<DTYPE>(src[nearest_src(sy, h, ph) * pw + nearest_src(sx, w, pw)]);
+                v = ld<DTYPE>(src[nearest_src(sy, h, ph) * pw + nearest_src(sx, w, pw)]);
             } else {
                 int iy0, iy1, ix0, ix1;
                 float wy0, wy1, wx0, wx1;
-                ppm_bilinear_src(sy, h, ph, iy0, iy1, wy0, wy1);
-                ppm_bilinear_src(sx, w, pw, ix0, ix1, wx0, wx1);
-                v = ppm_bilerp(ppm_ld<DTYPE>(src[iy0 * pw + ix0]), ppm_ld<DTYPE>(src[iy0 * pw + ix1]),
-                               ppm_ld<DTYPE>(src[iy1 * pw + ix0]), ppm_ld<DTYPE>(src[iy1 * pw + ix1]),
-                               wx0, wx1, wy0, wy1);
+                bilinear_src(sy, h, ph, iy0, iy1, wy0, wy1);
+                bilinear_src(sx, w, pw, ix0, ix1, wx0, wx1);
+                v = bilerp(ld<DTYPE>(src[iy0 * pw + ix0]), ld<DTYPE>(src[iy0 * pw + ix1]),
+                           ld<DTYPE>(src[iy1 * pw + ix0]), ld<DTYPE>(src[iy1 * pw + ix1]),
+                           wx0, wx1, wy0, wy1);
             }
-            op[i] = ppm_st<DTYPE>(v);
+            op[i] = st<DTYPE>(v);
         }
     }
 }
@@ -335,9 +296,9 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_upcat_fwd(
 // ------------------------------------------------------------------ upsample + concat backward
 template <int DTYPE, bool LDS>
 __global__ __launch_bounds__(PPM_THREADS) void k_ppm_upcat_bwd(
-    const typename ppm_elem<DTYPE>::type* __restrict__ g_out, const PpmDesc d)
+    const typename elem<DTYPE>::type* __restrict__ g_out, const PpmDesc d)
 {
-    typedef typename ppm_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     __shared__ float s_plane[LDS ? PPM_WAVES * PPM_LDS_PLANE : 1];
     __shared__ float s_rows[LDS ? PPM_WAVES * PPM_LDS_ROWS : 1];
     const int wave = threadIdx.x / kWave, lane = lane_id();
@@ -370,7 +331,7 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_upcat_bwd(
             float* pl = s_plane + wave * PPM_LDS_PLANE;
             float* rows = s_rows + wave * PPM_LDS_ROWS;
             if (valid)
-                for (uint32_t i = lane; i < d.HW; i += kWave) pl[i] = ppm_ld<DTYPE>(gp[i]);
+                for (uint32_t i = lane; i < d.HW; i += kWave) pl[i] = ld<DTYPE>(gp[i]);
             __syncthreads();
             if (valid)
                 for (int idx = lane; idx < H * pw; idx += kWave) {
@@ -395,7 +356,7 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_upcat_bwd(
                         float wy;
                         if (ppm_reads(d.mode, sy, h, ph, p, wy)) s = __fmaf_rn(rows[h * pw + q], wy, s);
                     }
-                    dst[cell] = ppm_st<DTYPE>(s);
+                    dst[cell] = st<DTYPE>(s);
                 }
             __syncthreads();
         } else {
@@ -413,19 +374,17 @@ __global__ __launch_bounds__(PPM_THREADS) void k_ppm_upcat_bwd(
                         for (int w = w0; w <= w1; ++w) {
                             float wx;
                             if (ppm_reads(d.mode, sx, w, pw, q, wx))
-                                r = __fmaf_rn(ppm_ld<DTYPE>(gp[h * W + w]), wx, r);
+                                r = __fmaf_rn(ld<DTYPE>(gp[h * W + w]), wx, r);
                         }
                         s = __fmaf_rn(r, wy, s);
                     }
-                    dst[cell] = ppm_st<DTYPE>(s);
+                    dst[cell] = st<DTYPE>(s);
                 }
         }
     }
 }
 
 // ------------------------------------------------------------------------------------ host side
-bool ppm_aligned(const void* p, int dtype) { return (uintptr_t)p % (dtype == NMSA_F32 ? 4u : 2u) == 0; }
-
 // sizes every entry point checks; NMSA_OK, NMSA_ERR_ARG or NMSA_ERR_UNSUPPORTED
 int ppm_check_sizes(int dtype, int B, int C, int H, int W, int n_bins, const int* ph, const int* pw)
 {
@@ -462,12 +421,6 @@ void ppm_desc(PpmDesc& d, int C, int H, int W, int n_bins, const int* ph, const 
     }
 }
 
-unsigned ppm_grid(uint64_t blocks)
-{
-    const uint64_t cap = (uint64_t)device_geometry().cus * PPM_BLOCKS_PER_CU;
-    return (unsigned)(blocks < cap ? blocks : cap);
-}
-
 // channel counts of an upcat call: NMSA_OK with the sum in `sum_cr`, or the error
 int ppm_check_channels(int B, int C, int n_bins, const int* cr, int64_t& sum_cr)
 {
@@ -499,17 +452,17 @@ extern "C" int nmsa_ppm_pool_fwd(const void* x, int dtype, int B, int C, int H, 
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = ppm_check_sizes(dtype, B, C, H, W, n_bins, ph, pw);
     if (rc != NMSA_OK) return rc;
-    if (!x || !pooled || !ppm_aligned(x, dtype)) return NMSA_ERR_ARG;
+    if (!x || !pooled || !elem_aligned(x, dtype)) return NMSA_ERR_ARG;
     for (int i = 0; i < n_bins; ++i)
-        if (!pooled[i] || !ppm_aligned(pooled[i], dtype)) return NMSA_ERR_ARG;
+        if (!pooled[i] || !elem_aligned(pooled[i], dtype)) return NMSA_ERR_ARG;
     PpmDesc d;
     ppm_desc(d, C, H, W, n_bins, ph, pw, nullptr, pooled, 0);
     d.planes = (uint32_t)(B * C);
     const bool lds = ppm_lds(H, W, n_bins, pw);
-    const dim3 grid(ppm_grid(((uint64_t)d.planes + PPM_WAVES - 1) / PPM_WAVES)), block(PPM_THREADS);
+    const dim3 grid(capped_grid(((uint64_t)d.planes + PPM_WAVES - 1) / PPM_WAVES, PPM_BLOCKS_PER_CU)), block(PPM_THREADS);
 #define PPM_POOL_FWD(DT)                                                                                    \
     do {                                                                                                    \
-        typedef ppm_elem<DT>::type S;                                                                       \
+        typedef elem<DT>::type S;                                                                           \
         if (lds) hipLaunchKernelGGL((k_ppm_pool_fwd<DT, true>), grid, block, 0, stream, (const S*)x, d);    \
         else hipLaunchKernelGGL((k_ppm_pool_fwd<DT, false>), grid, block, 0, stream, (const S*)x, d);       \
     } while (0)
@@ -525,9 +478,9 @@ extern "C" int nmsa_ppm_pool_bwd(const void* const* gp, int dtype, int B, int C,
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = ppm_check_sizes(dtype, B, C, H, W, n_bins, ph, pw);
     if (rc != NMSA_OK) return rc;
-    if (!gp || !gx || !ppm_aligned(gx, dtype)) return NMSA_ERR_ARG;
+    if (!gp || !gx || !elem_aligned(gx, dtype)) return NMSA_ERR_ARG;
     for (int i = 0; i < n_bins; ++i)
-        if (!ppm_aligned(gp[i], dtype)) return NMSA_ERR_ARG;      // NULL: that branch adds nothing
+        if (!elem_aligned(gp[i], dtype)) return NMSA_ERR_ARG;      // NULL: that branch adds nothing
     PpmDesc d;
     ppm_desc(d, C, H, W, n_bins, ph, pw, nullptr, (void* const*)gp, 0);
     d.planes = (uint32_t)(B * C);
@@ -537,7 +490,7 @@ extern "C" int nmsa_ppm_pool_bwd(const void* const* gp, int dtype, int B, int C,
     if (items > 0x7fffffffull) return NMSA_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)((items + PPM_WAVES - 1) / PPM_WAVES)), block(PPM_THREADS);
 #define PPM_POOL_BWD(DT)                                                                                    \
-    hipLaunchKernelGGL((k_ppm_pool_bwd<DT>), grid, block, 0, stream, (ppm_elem<DT>::type*)gx, d, side,      \
+    hipLaunchKernelGGL((k_ppm_pool_bwd<DT>), grid, block, 0, stream, (elem<DT>::type*)gx, d, side,          \
                        chunks, (uint32_t)items)
     NMSA_DISPATCH_DTYPE(dtype, PPM_POOL_BWD)
 #undef PPM_POOL_BWD
@@ -555,9 +508,9 @@ extern "C" int nmsa_ppm_upcat_fwd(const void* x, const void* const* ys, int dtyp
     if (mode != NMSA_PPM_NEAREST && mode != NMSA_PPM_BILINEAR) return NMSA_ERR_ARG;
     int64_t sum_cr = 0;
     if (int e = ppm_check_channels(B, C, n_bins, cr, sum_cr)) return e;
-    if (!x || !ys || !out || !ppm_aligned(x, dtype) || !ppm_aligned(out, dtype)) return NMSA_ERR_ARG;
+    if (!x || !ys || !out || !elem_aligned(x, dtype) || !elem_aligned(out, dtype)) return NMSA_ERR_ARG;
     for (int i = 0; i < n_bins; ++i)
-        if (!ys[i] || !ppm_aligned(ys[i], dtype)) return NMSA_ERR_ARG;
+        if (!ys[i] || !elem_aligned(ys[i], dtype)) return NMSA_ERR_ARG;
     PpmDesc d;
     ppm_desc(d, C, H, W, n_bins, ph, pw, cr, (void* const*)ys, mode);
     d.sum_cr = (uint32_t)sum_cr; d.c_total = (uint32_t)(C + sum_cr);
@@ -566,10 +519,10 @@ extern "C" int nmsa_ppm_upcat_fwd(const void* x, const void* const* ys, int dtyp
     const uint32_t chunks = (d.HW + run - 1) / run;
     const uint64_t items = (uint64_t)d.planes * chunks;
     if (items > 0x7fffffffull) return NMSA_ERR_UNSUPPORTED;
-    const dim3 grid(ppm_grid(items)), block(PPM_THREADS);
+    const dim3 grid(capped_grid(items, PPM_BLOCKS_PER_CU)), block(PPM_THREADS);
 #define PPM_UPCAT_FWD(DT)                                                                                   \
-    hipLaunchKernelGGL((k_ppm_upcat_fwd<DT>), grid, block, 0, stream, (const ppm_elem<DT>::type*)x,         \
-                       (ppm_elem<DT>::type*)out, d, chunks, (uint32_t)items)
+    hipLaunchKernelGGL((k_ppm_upcat_fwd<DT>), grid, block, 0, stream, (const elem<DT>::type*)x,             \
+                       (elem<DT>::type*)out, d, chunks, (uint32_t)items)
     NMSA_DISPATCH_DTYPE(dtype, PPM_UPCAT_FWD)
 #undef PPM_UPCAT_FWD
     return check_launch();
@@ -586,10 +539,10 @@ extern "C" int nmsa_ppm_upcat_bwd(const void* g_out, int dtype, int B, int C, in
     if (mode != NMSA_PPM_NEAREST && mode != NMSA_PPM_BILINEAR) return NMSA_ERR_ARG;
     int64_t sum_cr = 0;
     if (int e = ppm_check_channels(B, C, n_bins, cr, sum_cr)) return e;
-    if (!g_out || !gys || !ppm_aligned(g_out, dtype)) return NMSA_ERR_ARG;
+    if (!g_out || !gys || !elem_aligned(g_out, dtype)) return NMSA_ERR_ARG;
     bool any = false;
     for (int i = 0; i < n_bins; ++i) {
-        if (!ppm_aligned(gys[i], dtype)) return NMSA_ERR_ARG;    // NULL: that gradient is not wanted
+        if (!elem_aligned(gys[i], dtype)) return NMSA_ERR_ARG;    // NULL: that gradient is not wanted
         any = any || gys[i];
     }
     if (!any) return NMSA_OK;
@@ -598,10 +551,10 @@ extern "C" int nmsa_ppm_upcat_bwd(const void* g_out, int dtype, int B, int C, in
     d.sum_cr = (uint32_t)sum_cr; d.c_total = (uint32_t)(C + sum_cr);
     d.planes = (uint32_t)(B * sum_cr);
     const bool lds = ppm_lds(H, W, n_bins, pw);
-    const dim3 grid(ppm_grid(((uint64_t)d.planes + PPM_WAVES - 1) / PPM_WAVES)), block(PPM_THREADS);
+    const dim3 grid(capped_grid(((uint64_t)d.planes + PPM_WAVES - 1) / PPM_WAVES, PPM_BLOCKS_PER_CU)), block(PPM_THREADS);
 #define PPM_UPCAT_BWD(DT)                                                                                   \
     do {                                                                                                    \
-        typedef ppm_elem<DT>::type S;                                                                       \
+        typedef elem<DT>::type S;                                                                           \
         if (lds) hipLaunchKernelGGL((k_ppm_upcat_bwd<DT, true>), grid, block, 0, stream, (const S*)g_out, d); \
         else hipLaunchKernelGGL((k_ppm_upcat_bwd<DT, false>), grid, block, 0, stream, (const S*)g_out, d);  \
     } while (0)

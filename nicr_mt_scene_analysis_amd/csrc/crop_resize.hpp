@@ -1,6 +1,7 @@
 // crop_resize.hpp — geometry of "crop to the valid region, resize to the dataset resolution"
 // (reference model/postprocessing/dense_base.py:15-58), shared by every kernel that reads a
-// network-resolution map at full-resolution coordinates (resize.hip, normal.hip).
+// network-resolution map at full-resolution coordinates (resize.hip, normal.hip), and ATen's source
+// index and blend arithmetic for every kernel that resamples (context_module.hip, mlp_decoder.hip too).
 #pragma once
 #include "nmsa_common.hpp"
 
@@ -18,6 +19,28 @@ struct CropResize {
 __device__ __forceinline__ int nearest_src(float scale, int dst, int in)
 {
     return min((int)floorf(__fmul_rn((float)dst, scale)), in - 1);
+}
+
+// ATen's bilinear source (area_pixel_compute_source_index, align_corners = False): the two source
+// indices of `dst` and their weights
+__device__ __forceinline__ void bilinear_src(float scale, int dst, int in,
+                                             int& i0, int& i1, float& w0, float& w1)
+{
+    float s = __fmaf_rn(scale, __fadd_rn((float)dst, 0.5f), -0.5f);
+    s = (s < 0.f) ? 0.f : s;
+    i0 = min((int)s, in - 1);
+    i1 = min(i0 + 1, in - 1);
+    w1 = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
+    w0 = __fsub_rn(1.0f, w1);
+}
+
+// the blend (a*wx0 + b*wx1)*wy0 + (c*wx0 + d*wx1)*wy1 with one fused multiply-add per sum
+__device__ __forceinline__ float bilerp(float a, float b, float c, float d,
+                                        float wx0, float wx1, float wy0, float wy1)
+{
+    const float t0 = __fmaf_rn(a, wx0, __fmul_rn(b, wx1));
+    const float t1 = __fmaf_rn(c, wx0, __fmul_rn(d, wx1));
+    return __fmaf_rn(t0, wy0, __fmul_rn(t1, wy1));
 }
 
 inline bool bad_geometry(int planes, int Hs, int Ws, int y0, int x0, int h, int w, int Ho, int Wo)

@@ -27,7 +27,7 @@
 // Grids: the map kernels launch min(items, SEF_BLOCKS_PER_CU (SEF_BLOCK_ROUTE_PER_CU for the
 // 1024-lane workgroups) per compute unit of nmsa_device_geometry) workgroups and loop over the rest;
 // the excite kernels launch 2 * B workgroups.  Addressing: 32-bit, B*C*H*W < 2^31 is checked.
-#include "loss_common.hpp"
+#include "nmsa_common.hpp"
 #include <math.h>
 
 namespace nmsa {
@@ -43,26 +43,7 @@ constexpr int SEF_UNROLL = 4;
 constexpr int SEF_MAX_C = NMSA_SEFUSE_MAX_CHANNELS;
 constexpr int SEF_MAX_R = SEF_MAX_C / 16;
 
-template <int DTYPE> struct sef_elem { typedef uint16_t type; };
-template <> struct sef_elem<NMSA_F32> { typedef float type; };
-
-template <int DTYPE>
-__device__ __forceinline__ float sef_ld(typename sef_elem<DTYPE>::type v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
-    else return f16_to_f32(v);
-}
-
-template <int DTYPE>
-__device__ __forceinline__ typename sef_elem<DTYPE>::type sef_st(float v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
-    else return f32_to_f16(v);
-}
-
-template <typename S, int VEC> struct alignas(sizeof(S) * VEC) sef_pack { S v[VEC]; };
+// elem, ld, st, pack: nmsa_common.hpp
 
 // the four parameter tensors of both modalities, by value in the kernel arguments
 struct SefParams {
@@ -99,20 +80,20 @@ __device__ __forceinline__ float sef_act_grad(float g, float z)
 // chunk `c` (V elements from c * V) of a plane of HW elements as float32; ELEMENT route: what lies
 // behind the plane is +0
 template <int DTYPE, bool VECTOR>
-__device__ __forceinline__ void sef_chunk(const typename sef_elem<DTYPE>::type* __restrict__ plane, uint32_t c,
+__device__ __forceinline__ void sef_chunk(const typename elem<DTYPE>::type* __restrict__ plane, uint32_t c,
                                           uint32_t HW, float* out)
 {
-    typedef typename sef_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     if constexpr (VECTOR) {
-        const sef_pack<S, V> p = *(const sef_pack<S, V>*)(plane + c * V);
+        const pack<S, V> p = *(const pack<S, V>*)(plane + c * V);
 #pragma unroll
-        for (int j = 0; j < V; ++j) out[j] = sef_ld<DTYPE>(p.v[j]);
+        for (int j = 0; j < V; ++j) out[j] = ld<DTYPE>(p.v[j]);
     } else {
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             const uint32_t e = c * V + j;
-            out[j] = e < HW ? sef_ld<DTYPE>(plane[e]) : 0.0f;
+            out[j] = e < HW ? ld<DTYPE>(plane[e]) : 0.0f;
         }
     }
 }
@@ -144,10 +125,10 @@ __device__ __forceinline__ float sef_block_sum(float wave_sum, float* part)
 // s[m, plane] = S / float(HW), IEEE division; S in the order described in the file header
 template <int DTYPE, bool VECTOR, int PT>
 __global__ __launch_bounds__(PT == kWave ? SEF_THREADS : SEF_BLOCK_THREADS) void k_sefuse_squeeze(
-    const typename sef_elem<DTYPE>::type* __restrict__ x_rgb, const typename sef_elem<DTYPE>::type* __restrict__ x_depth,
+    const typename elem<DTYPE>::type* __restrict__ x_rgb, const typename elem<DTYPE>::type* __restrict__ x_depth,
     float* __restrict__ s, const uint32_t HW, const uint32_t planes, const uint32_t items)
 {
-    typedef typename sef_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     __shared__ float part[SEF_BLOCK_WAVES];
     const uint32_t chunks = (HW + V - 1) / V;
@@ -182,11 +163,11 @@ __global__ __launch_bounds__(PT == kWave ? SEF_THREADS : SEF_BLOCK_THREADS) void
 // both modalities from one read of gy; a NULL x_m: that half of gw is not written
 template <int DTYPE, bool VECTOR, int PT>
 __global__ __launch_bounds__(PT == kWave ? SEF_THREADS : SEF_BLOCK_THREADS) void k_sefuse_wgrad(
-    const typename sef_elem<DTYPE>::type* __restrict__ gy, const typename sef_elem<DTYPE>::type* __restrict__ x_rgb,
-    const typename sef_elem<DTYPE>::type* __restrict__ x_depth, float* __restrict__ gw, const uint32_t HW,
+    const typename elem<DTYPE>::type* __restrict__ gy, const typename elem<DTYPE>::type* __restrict__ x_rgb,
+    const typename elem<DTYPE>::type* __restrict__ x_depth, float* __restrict__ gw, const uint32_t HW,
     const uint32_t planes, const uint32_t items)
 {
-    typedef typename sef_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr int V = 16 / sizeof(S);
     __shared__ float part[SEF_BLOCK_WAVES];
     const uint32_t chunks = (HW + V - 1) / V;
@@ -317,11 +298,11 @@ __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_excite_bwd(
 // y = round(x_rgb * w_rgb + x_depth * w_depth): two products, one sum, each rounded to float32
 template <int DTYPE, int VEC>
 __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_scale_add(
-    const typename sef_elem<DTYPE>::type* __restrict__ x_rgb, const typename sef_elem<DTYPE>::type* __restrict__ x_depth,
-    const float* __restrict__ w, typename sef_elem<DTYPE>::type* __restrict__ y, const uint32_t HW,
+    const typename elem<DTYPE>::type* __restrict__ x_rgb, const typename elem<DTYPE>::type* __restrict__ x_depth,
+    const float* __restrict__ w, typename elem<DTYPE>::type* __restrict__ y, const uint32_t HW,
     const uint32_t planes, const uint32_t nvec, const uint32_t items)
 {
-    typedef sef_pack<typename sef_elem<DTYPE>::type, VEC> P;
+    typedef pack<typename elem<DTYPE>::type, VEC> P;
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
 #pragma unroll
         for (int u = 0; u < SEF_UNROLL; ++u) {
@@ -334,7 +315,7 @@ __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_scale_add(
             P r;
 #pragma unroll
             for (int k = 0; k < VEC; ++k)
-                r.v[k] = sef_st<DTYPE>(__fadd_rn(__fmul_rn(sef_ld<DTYPE>(a.v[k]), wr), __fmul_rn(sef_ld<DTYPE>(b.v[k]), wd)));
+                r.v[k] = st<DTYPE>(__fadd_rn(__fmul_rn(ld<DTYPE>(a.v[k]), wr), __fmul_rn(ld<DTYPE>(b.v[k]), wd)));
             *(P*)(y + e) = r;
         }
     }
@@ -345,11 +326,11 @@ __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_scale_add(
 // a NULL gx_m is not wanted
 template <int DTYPE, int VEC>
 __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_apply(
-    const typename sef_elem<DTYPE>::type* __restrict__ gy, const float* __restrict__ w, const float* __restrict__ gs,
-    typename sef_elem<DTYPE>::type* __restrict__ gx_rgb, typename sef_elem<DTYPE>::type* __restrict__ gx_depth,
+    const typename elem<DTYPE>::type* __restrict__ gy, const float* __restrict__ w, const float* __restrict__ gs,
+    typename elem<DTYPE>::type* __restrict__ gx_rgb, typename elem<DTYPE>::type* __restrict__ gx_depth,
     const uint32_t HW, const uint32_t planes, const uint32_t nvec, const uint32_t items)
 {
-    typedef sef_pack<typename sef_elem<DTYPE>::type, VEC> P;
+    typedef pack<typename elem<DTYPE>::type, VEC> P;
     const float fhw = (float)HW;
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
 #pragma unroll
@@ -361,19 +342,19 @@ __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_apply(
             const P g = *(const P*)(gy + e);
             float f[VEC];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) f[k] = sef_ld<DTYPE>(g.v[k]);
+            for (int k = 0; k < VEC; ++k) f[k] = ld<DTYPE>(g.v[k]);
             if (gx_rgb) {
                 const float wm = w[plane], q = __fdiv_rn(gs[plane], fhw);
                 P r;
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) r.v[k] = sef_st<DTYPE>(__fadd_rn(__fmul_rn(f[k], wm), q));
+                for (int k = 0; k < VEC; ++k) r.v[k] = st<DTYPE>(__fadd_rn(__fmul_rn(f[k], wm), q));
                 *(P*)(gx_rgb + e) = r;
             }
             if (gx_depth) {
                 const float wm = w[planes + plane], q = __fdiv_rn(gs[planes + plane], fhw);
                 P r;
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) r.v[k] = sef_st<DTYPE>(__fadd_rn(__fmul_rn(f[k], wm), q));
+                for (int k = 0; k < VEC; ++k) r.v[k] = st<DTYPE>(__fadd_rn(__fmul_rn(f[k], wm), q));
                 *(P*)(gx_depth + e) = r;
             }
         }
@@ -381,9 +362,7 @@ __global__ __launch_bounds__(SEF_THREADS) void k_sefuse_apply(
 }
 
 // ------------------------------------------------------------------------------------ host side
-bool sef_aligned(const void* p, int dtype) { return (uintptr_t)p % (dtype == NMSA_F32 ? 4u : 2u) == 0; }
-bool sef_f32(const void* p) { return (uintptr_t)p % 4u == 0; }
-bool sef_on16(const void* p) { return !p || (uintptr_t)p % 16u == 0; }
+bool sef_f32(const void* p) { return aligned(p, 4); }
 int sef_vec(int dtype) { return dtype == NMSA_F32 ? 4 : 8; }
 
 // sizes of a map call: NMSA_OK, NMSA_ERR_ARG or NMSA_ERR_UNSUPPORTED (to be reported after the other
@@ -408,16 +387,10 @@ int sef_check_vec(int act, int B, int C)
 // of the call on 16 bytes (a NULL tensor is not part of the call)
 bool sef_vector(const void* t0, const void* t1, const void* t2, int dtype, int64_t HW)
 {
-    return HW % sef_vec(dtype) == 0 && sef_on16(t0) && sef_on16(t1) && sef_on16(t2);
+    return HW % sef_vec(dtype) == 0 && aligned(t0, 16) && aligned(t1, 16) && aligned(t2, 16);
 }
 
 bool sef_wave_route(int64_t HW) { return HW <= NMSA_SEFUSE_WAVE_PLANE_MAX; }
-
-unsigned sef_grid(uint64_t items, int per_cu)
-{
-    const uint64_t cap = (uint64_t)device_geometry().cus * per_cu;
-    return (unsigned)(items < cap ? items : cap);
-}
 
 }  // namespace
 }  // namespace nmsa
@@ -427,7 +400,7 @@ extern "C" int nmsa_sefuse_route(const void* t0, const void* t1, const void* t2,
     using namespace nmsa;
     const int rc = sef_check_map(dtype, 1, 16, H, W);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!t0 || !sef_aligned(t0, dtype) || !sef_aligned(t1, dtype) || !sef_aligned(t2, dtype)) return NMSA_ERR_ARG;
+    if (!t0 || !elem_aligned(t0, dtype) || !elem_aligned(t1, dtype) || !elem_aligned(t2, dtype)) return NMSA_ERR_ARG;
     if (rc != NMSA_OK) return rc;
     const int64_t HW = (int64_t)H * W;
     return (sef_vector(t0, t1, t2, dtype, HW) ? NMSA_SEFUSE_ROUTE_VECTOR : NMSA_SEFUSE_ROUTE_ELEMENT) |
@@ -450,17 +423,17 @@ extern "C" int nmsa_sefuse_squeeze(const void* x_rgb, const void* x_depth, int d
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = sef_check_map(dtype, B, C, H, W);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!x_rgb || !x_depth || !s || !sef_aligned(x_rgb, dtype) || !sef_aligned(x_depth, dtype) || !sef_f32(s))
+    if (!x_rgb || !x_depth || !s || !elem_aligned(x_rgb, dtype) || !elem_aligned(x_depth, dtype) || !sef_f32(s))
         return NMSA_ERR_ARG;
     if (rc != NMSA_OK) return rc;
     const uint32_t HW = (uint32_t)(H * W), planes = (uint32_t)(B * C);
     const bool vector = sef_vector(x_rgb, x_depth, nullptr, dtype, HW), wave = sef_wave_route(HW);
     const uint64_t items = wave ? ((uint64_t)2 * planes + SEF_WAVES - 1) / SEF_WAVES : (uint64_t)2 * planes;
-    const dim3 grid(sef_grid(items, wave ? SEF_BLOCKS_PER_CU : SEF_BLOCK_ROUTE_PER_CU));
+    const dim3 grid(capped_grid(items, wave ? SEF_BLOCKS_PER_CU : SEF_BLOCK_ROUTE_PER_CU));
     const dim3 block(wave ? SEF_THREADS : SEF_BLOCK_THREADS);
 #define SEF_SQUEEZE_ONE(DT, VECTOR, PT)                                                                     \
     hipLaunchKernelGGL((k_sefuse_squeeze<DT, VECTOR, PT>), grid, block, 0, stream,                          \
-                       (const sef_elem<DT>::type*)x_rgb, (const sef_elem<DT>::type*)x_depth, s, HW, planes, \
+                       (const elem<DT>::type*)x_rgb, (const elem<DT>::type*)x_depth, s, HW, planes,         \
                        (uint32_t)items)
 #define SEF_SQUEEZE(DT) SEF_DISPATCH_REDUCE(DT, SEF_SQUEEZE_ONE)
     NMSA_DISPATCH_DTYPE(dtype, SEF_SQUEEZE)
@@ -476,7 +449,7 @@ extern "C" int nmsa_sefuse_weight_grad(const void* gy, const void* x_rgb, const 
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = sef_check_map(dtype, B, C, H, W);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!gy || !gw || !sef_aligned(gy, dtype) || !sef_aligned(x_rgb, dtype) || !sef_aligned(x_depth, dtype) ||
+    if (!gy || !gw || !elem_aligned(gy, dtype) || !elem_aligned(x_rgb, dtype) || !elem_aligned(x_depth, dtype) ||
         !sef_f32(gw))
         return NMSA_ERR_ARG;
     if (rc != NMSA_OK) return rc;
@@ -484,11 +457,11 @@ extern "C" int nmsa_sefuse_weight_grad(const void* gy, const void* x_rgb, const 
     const uint32_t HW = (uint32_t)(H * W), planes = (uint32_t)(B * C);
     const bool vector = sef_vector(gy, x_rgb, x_depth, dtype, HW), wave = sef_wave_route(HW);
     const uint64_t items = wave ? ((uint64_t)planes + SEF_WAVES - 1) / SEF_WAVES : (uint64_t)planes;
-    const dim3 grid(sef_grid(items, wave ? SEF_BLOCKS_PER_CU : SEF_BLOCK_ROUTE_PER_CU));
+    const dim3 grid(capped_grid(items, wave ? SEF_BLOCKS_PER_CU : SEF_BLOCK_ROUTE_PER_CU));
     const dim3 block(wave ? SEF_THREADS : SEF_BLOCK_THREADS);
 #define SEF_WGRAD_ONE(DT, VECTOR, PT)                                                                          \
-    hipLaunchKernelGGL((k_sefuse_wgrad<DT, VECTOR, PT>), grid, block, 0, stream, (const sef_elem<DT>::type*)gy, \
-                       (const sef_elem<DT>::type*)x_rgb, (const sef_elem<DT>::type*)x_depth, gw, HW, planes,   \
+    hipLaunchKernelGGL((k_sefuse_wgrad<DT, VECTOR, PT>), grid, block, 0, stream, (const elem<DT>::type*)gy,    \
+                       (const elem<DT>::type*)x_rgb, (const elem<DT>::type*)x_depth, gw, HW, planes,           \
                        (uint32_t)items)
 #define SEF_WGRAD(DT) SEF_DISPATCH_REDUCE(DT, SEF_WGRAD_ONE)
     NMSA_DISPATCH_DTYPE(dtype, SEF_WGRAD)
@@ -562,8 +535,8 @@ extern "C" int nmsa_sefuse_scale_add(const void* x_rgb, const void* x_depth, int
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = sef_check_map(dtype, B, C, H, W);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!x_rgb || !x_depth || !w || !y || !sef_aligned(x_rgb, dtype) || !sef_aligned(x_depth, dtype) ||
-        !sef_aligned(y, dtype) || !sef_f32(w))
+    if (!x_rgb || !x_depth || !w || !y || !elem_aligned(x_rgb, dtype) || !elem_aligned(x_depth, dtype) ||
+        !elem_aligned(y, dtype) || !sef_f32(w))
         return NMSA_ERR_ARG;
     if (rc != NMSA_OK) return rc;
     const uint32_t HW = (uint32_t)(H * W), planes = (uint32_t)(B * C);
@@ -571,10 +544,10 @@ extern "C" int nmsa_sefuse_scale_add(const void* x_rgb, const void* x_depth, int
     const uint32_t nvec = (uint32_t)((uint64_t)planes * HW / (vector ? sef_vec(dtype) : 1));
     const uint64_t per_item = (uint64_t)SEF_THREADS * SEF_UNROLL;
     const uint64_t items = (nvec + per_item - 1) / per_item;
-    const dim3 grid(sef_grid(items, SEF_BLOCKS_PER_CU)), block(SEF_THREADS);
+    const dim3 grid(capped_grid(items, SEF_BLOCKS_PER_CU)), block(SEF_THREADS);
 #define SEF_SCALE_ADD(DT)                                                                                      \
     do {                                                                                                       \
-        typedef sef_elem<DT>::type S;                                                                          \
+        typedef elem<DT>::type S;                                                                              \
         if (vector)                                                                                            \
             hipLaunchKernelGGL((k_sefuse_scale_add<DT, 16 / sizeof(S)>), grid, block, 0, stream, (const S*)x_rgb, \
                                (const S*)x_depth, w, (S*)y, HW, planes, nvec, (uint32_t)items);                \
@@ -594,7 +567,7 @@ extern "C" int nmsa_sefuse_apply_bwd(const void* gy, int dtype, const float* w, 
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = sef_check_map(dtype, B, C, H, W);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!gy || !w || !gs || !sef_aligned(gy, dtype) || !sef_aligned(gx_rgb, dtype) || !sef_aligned(gx_depth, dtype) ||
+    if (!gy || !w || !gs || !elem_aligned(gy, dtype) || !elem_aligned(gx_rgb, dtype) || !elem_aligned(gx_depth, dtype) ||
         !sef_f32(w) || !sef_f32(gs))
         return NMSA_ERR_ARG;
     if (rc != NMSA_OK) return rc;
@@ -604,10 +577,10 @@ extern "C" int nmsa_sefuse_apply_bwd(const void* gy, int dtype, const float* w, 
     const uint32_t nvec = (uint32_t)((uint64_t)planes * HW / (vector ? sef_vec(dtype) : 1));
     const uint64_t per_item = (uint64_t)SEF_THREADS * SEF_UNROLL;
     const uint64_t items = (nvec + per_item - 1) / per_item;
-    const dim3 grid(sef_grid(items, SEF_BLOCKS_PER_CU)), block(SEF_THREADS);
+    const dim3 grid(capped_grid(items, SEF_BLOCKS_PER_CU)), block(SEF_THREADS);
 #define SEF_APPLY(DT)                                                                                         \
     do {                                                                                                      \
-        typedef sef_elem<DT>::type S;                                                                         \
+        typedef elem<DT>::type S;                                                                             \
         if (vector)                                                                                           \
             hipLaunchKernelGGL((k_sefuse_apply<DT, 16 / sizeof(S)>), grid, block, 0, stream, (const S*)gy, w, gs, \
                                (S*)gx_rgb, (S*)gx_depth, HW, planes, nvec, (uint32_t)items);                  \

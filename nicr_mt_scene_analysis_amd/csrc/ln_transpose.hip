@@ -45,7 +45,7 @@
 // of the 64 banks, the next row the other half; element route: 32 lanes read one row.
 // The grid is min(tiles, 8 (fwd) / 4 (bwd) workgroups per compute unit of nmsa_device_geometry),
 // grid-stride; B*P*C < 2^31 is checked, so every offset fits 32 bits (64-bit here all the same).
-#include "loss_common.hpp"
+#include "nmsa_common.hpp"
 #include <math.h>
 
 namespace nmsa {
@@ -62,59 +62,37 @@ constexpr int LNT_FWD_BLOCKS_PER_CU = 8;
 constexpr int LNT_BWD_BLOCKS_PER_CU = 4;
 constexpr int LNT_REDUCE_COLS = 32, LNT_REDUCE_PARTS = 8;
 
-template <typename T, int N>
-struct alignas(sizeof(T) * N > 16 ? 16 : sizeof(T) * N) lnt_pack {
-    T v[N];
-};
-
-template <int DTYPE> struct lnt_elem { typedef uint16_t type; };
-template <> struct lnt_elem<NMSA_F32> { typedef float type; };
-
-template <int DTYPE>
-__device__ __forceinline__ float lnt_ld(typename lnt_elem<DTYPE>::type v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
-    else return f16_to_f32(v);
-}
-
-template <int DTYPE>
-__device__ __forceinline__ typename lnt_elem<DTYPE>::type lnt_st(float v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
-    else return f32_to_f16(v);
-}
+// elem, ld, st, pack: nmsa_common.hpp
 
 // N elements from p.  Vector route: one 16-byte access (all N are there).  Element route: the
 // first `valid` of them one by one, 0 for the rest.
 template <int DTYPE, int N, bool VEC>
-__device__ __forceinline__ void lnt_load(const typename lnt_elem<DTYPE>::type* p, float* out, uint32_t valid)
+__device__ __forceinline__ void lnt_load(const typename elem<DTYPE>::type* p, float* out, uint32_t valid)
 {
-    typedef typename lnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     if constexpr (VEC) {
-        const lnt_pack<S, N> v = *(const lnt_pack<S, N>*)p;
+        const pack<S, N> v = *(const pack<S, N>*)p;
 #pragma unroll
-        for (int j = 0; j < N; ++j) out[j] = lnt_ld<DTYPE>(v.v[j]);
+        for (int j = 0; j < N; ++j) out[j] = ld<DTYPE>(v.v[j]);
     } else {
 #pragma unroll
-        for (int j = 0; j < N; ++j) out[j] = (uint32_t)j < valid ? lnt_ld<DTYPE>(p[j]) : 0.0f;
+        for (int j = 0; j < N; ++j) out[j] = (uint32_t)j < valid ? ld<DTYPE>(p[j]) : 0.0f;
     }
 }
 
 template <int DTYPE, int N, bool VEC>
-__device__ __forceinline__ void lnt_store(typename lnt_elem<DTYPE>::type* p, const float* in, uint32_t valid)
+__device__ __forceinline__ void lnt_store(typename elem<DTYPE>::type* p, const float* in, uint32_t valid)
 {
-    typedef typename lnt_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     if constexpr (VEC) {
-        lnt_pack<S, N> v;
+        pack<S, N> v;
 #pragma unroll
-        for (int j = 0; j < N; ++j) v.v[j] = lnt_st<DTYPE>(in[j]);
-        *(lnt_pack<S, N>*)p = v;
+        for (int j = 0; j < N; ++j) v.v[j] = st<DTYPE>(in[j]);
+        *(pack<S, N>*)p = v;
     } else {
 #pragma unroll
         for (int j = 0; j < N; ++j)
-            if ((uint32_t)j < valid) p[j] = lnt_st<DTYPE>(in[j]);
+            if ((uint32_t)j < valid) p[j] = st<DTYPE>(in[j]);
     }
 }
 
@@ -161,7 +139,7 @@ __device__ __forceinline__ float lnt_wave_sum(float v)
 
 // y side, global -> LDS image (vector route: runs of VY pixels, element route: single elements)
 template <int DY, int V, int VY, bool VEC>
-__device__ __forceinline__ void lnt_image_from_global(const typename lnt_elem<DY>::type* src, float* tile,
+__device__ __forceinline__ void lnt_image_from_global(const typename elem<DY>::type* src, float* tile,
                                                       uint32_t b, uint32_t p0, uint32_t np, uint32_t c0,
                                                       const LntGeom& g)
 {
@@ -187,7 +165,7 @@ __device__ __forceinline__ void lnt_image_from_global(const typename lnt_elem<DY
 // S: slots of a row a lane holds, S*V values; R = 32 / (S*V) rows are loaded together, so a short row
 // (C <= 64V: one slot) has 8 (float32) / 4 (half) rows in flight per wave and a tree of V values only.
 template <int DX, bool VEC, int S>
-__device__ __forceinline__ void lnt_stats(const typename lnt_elem<DX>::type* xt, size_t row0, uint32_t np,
+__device__ __forceinline__ void lnt_stats(const typename elem<DX>::type* xt, size_t row0, uint32_t np,
                                           uint32_t wave, uint32_t lane, const LntGeom& g, float* s_mean,
                                           float* s_rstd, float* __restrict__ mean_out, float* __restrict__ rstd_out)
 {
@@ -254,12 +232,12 @@ __device__ __forceinline__ void lnt_stats(const typename lnt_elem<DX>::type* xt,
 
 template <int DX, int DY, bool VEC>
 __global__ __launch_bounds__(LNT_THREADS) void k_lnt_fwd(
-    const typename lnt_elem<DX>::type* __restrict__ x, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const typename lnt_elem<DY>::type* __restrict__ add,
-    typename lnt_elem<DY>::type* __restrict__ y, float* __restrict__ mean_out, float* __restrict__ rstd_out,
+    const typename elem<DX>::type* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const typename elem<DY>::type* __restrict__ add,
+    typename elem<DY>::type* __restrict__ y, float* __restrict__ mean_out, float* __restrict__ rstd_out,
     const LntGeom g)
 {
-    typedef typename lnt_elem<DX>::type SX;
+    typedef typename elem<DX>::type SX;
     constexpr int V = lnt_vec(DX), VY = VEC ? lnt_vec(DY) : 1;
     constexpr int NCB = LNT_CC / (16 * V), RPR = LNT_TP / VY;
     __shared__ __attribute__((aligned(16))) float tile[LNT_CC * LNT_TP];
@@ -329,11 +307,11 @@ __global__ __launch_bounds__(LNT_THREADS) void k_lnt_fwd(
 
 template <int DX, int DY, bool VEC>
 __global__ __launch_bounds__(LNT_THREADS) void k_lnt_bwd(
-    const typename lnt_elem<DY>::type* __restrict__ gy, const typename lnt_elem<DX>::type* __restrict__ x,
+    const typename elem<DY>::type* __restrict__ gy, const typename elem<DX>::type* __restrict__ x,
     const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
-    typename lnt_elem<DX>::type* __restrict__ gx, float* __restrict__ partials, const LntGeom g)
+    typename elem<DX>::type* __restrict__ gx, float* __restrict__ partials, const LntGeom g)
 {
-    typedef typename lnt_elem<DX>::type SX;
+    typedef typename elem<DX>::type SX;
     constexpr int V = lnt_vec(DX), VY = VEC ? lnt_vec(DY) : 1;
     constexpr int NCB = LNT_CC / (16 * V);
     constexpr int TREE = LNT_MAX_SLOTS / 8;         // partials of a pixel per tree lane
@@ -512,9 +490,7 @@ __global__ __launch_bounds__(LNT_REDUCE_COLS * LNT_REDUCE_PARTS) void k_lnt_redu
     }
 }
 
-int lnt_elem_bytes(int dtype) { return dtype == NMSA_F32 ? 4 : 2; }
 bool lnt_is_dtype(int dtype) { return dtype == NMSA_F32 || dtype == NMSA_BF16 || dtype == NMSA_F16; }
-bool lnt_aligned(const void* p, uintptr_t n) { return (uintptr_t)p % n == 0; }
 
 // dtypes and sizes every entry point checks; NMSA_OK, NMSA_ERR_ARG or NMSA_ERR_UNSUPPORTED
 int lnt_check_sizes(int dtype_x, int dtype_y, int B, int P, int C)
@@ -530,8 +506,8 @@ int lnt_check_sizes(int dtype_x, int dtype_y, int B, int P, int C)
 // and every tensor of the call on 16 bytes (a NULL pointer is no tensor of the call)
 bool lnt_vector(int dtype_x, int dtype_y, int P, int C, const void* a, const void* b, const void* c)
 {
-    return C % lnt_vec(dtype_x) == 0 && P % lnt_vec(dtype_y) == 0 && lnt_aligned(a, 16) && lnt_aligned(b, 16) &&
-           lnt_aligned(c, 16);
+    return C % lnt_vec(dtype_x) == 0 && P % lnt_vec(dtype_y) == 0 && aligned(a, 16) && aligned(b, 16) &&
+           aligned(c, 16);
 }
 
 LntGeom lnt_geometry(int B, int P, int C, float eps)
@@ -541,12 +517,6 @@ LntGeom lnt_geometry(int B, int P, int C, float eps)
     g.tiles_per_image = (uint32_t)((P + LNT_TP - 1) / LNT_TP);
     g.tiles = (uint32_t)B * g.tiles_per_image;                      // <= B * P < 2^31
     return g;
-}
-
-unsigned lnt_grid(const LntGeom& g, int blocks_per_cu)
-{
-    const uint64_t cap = (uint64_t)device_geometry().cus * blocks_per_cu;
-    return (unsigned)(g.tiles < cap ? g.tiles : cap);
 }
 
 }  // namespace
@@ -568,8 +538,8 @@ extern "C" int nmsa_ln_nhwc_nchw_route(const void* x, const void* y, int dtype_x
     using namespace nmsa;
     const int rc = lnt_check_sizes(dtype_x, dtype_y, B, P, C);
     if (rc != NMSA_OK) return rc;
-    if (!x || !y || !lnt_aligned(x, (uintptr_t)lnt_elem_bytes(dtype_x)) ||
-        !lnt_aligned(y, (uintptr_t)lnt_elem_bytes(dtype_y)))
+    if (!x || !y || !aligned(x, (uintptr_t)elem_bytes(dtype_x)) ||
+        !aligned(y, (uintptr_t)elem_bytes(dtype_y)))
         return NMSA_ERR_ARG;
     return lnt_vector(dtype_x, dtype_y, P, C, x, y, nullptr) ? NMSA_LNT_ROUTE_VECTOR : NMSA_LNT_ROUTE_ELEMENT;
 }
@@ -582,19 +552,19 @@ extern "C" int nmsa_ln_nhwc_nchw_fwd(const void* x, int dtype_x, const float* ga
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = lnt_check_sizes(dtype_x, dtype_y, B, P, C);
     if (rc != NMSA_OK) return rc;
-    const uintptr_t ex = (uintptr_t)lnt_elem_bytes(dtype_x), ey = (uintptr_t)lnt_elem_bytes(dtype_y);
+    const uintptr_t ex = (uintptr_t)elem_bytes(dtype_x), ey = (uintptr_t)elem_bytes(dtype_y);
     if (!x || !y || !gamma || !beta || (mean == nullptr) != (rstd == nullptr)) return NMSA_ERR_ARG;
     if (!(eps >= 0.0f) || isinf(eps)) return NMSA_ERR_ARG;
-    if (!lnt_aligned(x, ex) || !lnt_aligned(y, ey) || !lnt_aligned(add, ey) || !lnt_aligned(gamma, 4) ||
-        !lnt_aligned(beta, 4) || !lnt_aligned(mean, 4) || !lnt_aligned(rstd, 4))
+    if (!aligned(x, ex) || !aligned(y, ey) || !aligned(add, ey) || !aligned(gamma, 4) ||
+        !aligned(beta, 4) || !aligned(mean, 4) || !aligned(rstd, 4))
         return NMSA_ERR_ARG;
     const bool vec = lnt_vector(dtype_x, dtype_y, P, C, x, y, add);
     const LntGeom g = lnt_geometry(B, P, C, eps);
-    const dim3 grid(lnt_grid(g, LNT_FWD_BLOCKS_PER_CU)), block(LNT_THREADS);
+    const dim3 grid(capped_grid(g.tiles, LNT_FWD_BLOCKS_PER_CU)), block(LNT_THREADS);
 #define LNT_FWD(DX, DY)                                                                                     \
     do {                                                                                                    \
-        typedef lnt_elem<DX>::type SX;                                                                      \
-        typedef lnt_elem<DY>::type SY;                                                                      \
+        typedef elem<DX>::type SX;                                                                          \
+        typedef elem<DY>::type SY;                                                                          \
         if (vec) hipLaunchKernelGGL((k_lnt_fwd<DX, DY, true>), grid, block, 0, stream, (const SX*)x, gamma, \
                                     beta, (const SY*)add, (SY*)y, mean, rstd, g);                           \
         else hipLaunchKernelGGL((k_lnt_fwd<DX, DY, false>), grid, block, 0, stream, (const SX*)x, gamma,    \
@@ -610,7 +580,7 @@ extern "C" size_t nmsa_ln_nhwc_nchw_bwd_workspace_bytes(int B, int P, int C)
     using namespace nmsa;
     if (lnt_check_sizes(NMSA_F32, NMSA_F32, B, P, C) != NMSA_OK) return 0;
     const LntGeom g = lnt_geometry(B, P, C, 0.0f);
-    return (size_t)lnt_grid(g, LNT_BWD_BLOCKS_PER_CU) * 2 * (size_t)C * sizeof(float);
+    return (size_t)capped_grid(g.tiles, LNT_BWD_BLOCKS_PER_CU) * 2 * (size_t)C * sizeof(float);
 }
 
 extern "C" int nmsa_ln_nhwc_nchw_bwd(const void* gy, int dtype_y, const void* x, int dtype_x,
@@ -622,16 +592,16 @@ extern "C" int nmsa_ln_nhwc_nchw_bwd(const void* gy, int dtype_y, const void* x,
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = lnt_check_sizes(dtype_x, dtype_y, B, P, C);
     if (rc != NMSA_OK) return rc;
-    const uintptr_t ex = (uintptr_t)lnt_elem_bytes(dtype_x), ey = (uintptr_t)lnt_elem_bytes(dtype_y);
+    const uintptr_t ex = (uintptr_t)elem_bytes(dtype_x), ey = (uintptr_t)elem_bytes(dtype_y);
     if (!gy || !x || !gamma || !mean || !rstd) return NMSA_ERR_ARG;
-    if (!lnt_aligned(gy, ey) || !lnt_aligned(x, ex) || !lnt_aligned(gx, ex) || !lnt_aligned(gamma, 4) ||
-        !lnt_aligned(mean, 4) || !lnt_aligned(rstd, 4) || !lnt_aligned(ggamma, 4) || !lnt_aligned(gbeta, 4))
+    if (!aligned(gy, ey) || !aligned(x, ex) || !aligned(gx, ex) || !aligned(gamma, 4) ||
+        !aligned(mean, 4) || !aligned(rstd, 4) || !aligned(ggamma, 4) || !aligned(gbeta, 4))
         return NMSA_ERR_ARG;
     const bool reduce = ggamma || gbeta;
     const LntGeom g = lnt_geometry(B, P, C, 0.0f);
-    const unsigned nwg = lnt_grid(g, LNT_BWD_BLOCKS_PER_CU);
+    const unsigned nwg = capped_grid(g.tiles, LNT_BWD_BLOCKS_PER_CU);
     if (reduce) {
-        if (!workspace || !lnt_aligned(workspace, 16)) return NMSA_ERR_ARG;
+        if (!workspace || !aligned(workspace, 16)) return NMSA_ERR_ARG;
         if (workspace_bytes < (size_t)nwg * 2 * (size_t)C * sizeof(float)) return NMSA_ERR_WORKSPACE;
     }
     if (!gx && !reduce) return NMSA_OK;
@@ -640,8 +610,8 @@ extern "C" int nmsa_ln_nhwc_nchw_bwd(const void* gy, int dtype_y, const void* x,
     const dim3 grid(nwg), block(LNT_THREADS);
 #define LNT_BWD(DX, DY)                                                                                     \
     do {                                                                                                    \
-        typedef lnt_elem<DX>::type SX;                                                                      \
-        typedef lnt_elem<DY>::type SY;                                                                      \
+        typedef elem<DX>::type SX;                                                                          \
+        typedef elem<DY>::type SY;                                                                          \
         if (vec) hipLaunchKernelGGL((k_lnt_bwd<DX, DY, true>), grid, block, 0, stream, (const SY*)gy,       \
                                     (const SX*)x, gamma, mean, rstd, (SX*)gx, partials, g);                 \
         else hipLaunchKernelGGL((k_lnt_bwd<DX, DY, false>), grid, block, 0, stream, (const SY*)gy,          \

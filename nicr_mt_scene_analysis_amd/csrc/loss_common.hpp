@@ -3,15 +3,6 @@
 #pragma once
 #include "nmsa_common.hpp"
 
-// run CALL(<dtype constant>) for the runtime dtype code (host side)
-#define NMSA_DISPATCH_DTYPE(dtype, CALL)          \
-    switch (dtype) {                              \
-        case NMSA_F32: CALL(NMSA_F32); break;     \
-        case NMSA_BF16: CALL(NMSA_BF16); break;   \
-        case NMSA_F16: CALL(NMSA_F16); break;     \
-        default: return NMSA_ERR_ARG;             \
-    }
-
 namespace nmsa {
 
 constexpr int LOSS_THREADS = 256;
@@ -19,22 +10,11 @@ constexpr int LOSS_THREADS = 256;
 // one per workgroup; summed in a FIXED order by k_loss_finalize (deterministic results)
 struct LossPartial { double sum; double aux; long long count; long long pad; };
 
-typedef float f32x4_s __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4_s __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_s __attribute__((ext_vector_type(2)));
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ uint16_t f32_to_bf16(float f)
-{
-    // round-to-nearest-even via the hardware conversion (keeps NaN a NaN)
-    return __builtin_bit_cast(uint16_t, (__bf16)f);
-}
-__device__ __forceinline__ uint16_t f32_to_f16(float f)
-{
-    return __builtin_bit_cast(uint16_t, (_Float16)f);
-}
 
 // element j (0..1) of a dword holding two 16-bit values / the dword itself for f32
 template <int DTYPE>

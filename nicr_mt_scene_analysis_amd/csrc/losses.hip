@@ -430,20 +430,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_vm_fused(
 //   (ATen cosine_embedding_loss); y = lut[b][index-1]
 // one px per lane: plane reads are coalesced across lanes, LUT rows come from L2
 // =================================================================================
-template <int DTYPE>
-__device__ __forceinline__ float ld1(const void* base, size_t off)
-{
-    if (DTYPE == NMSA_F32) return ((const float*)base)[off];
-    const uint16_t h = ((const uint16_t*)base)[off];
-    return (DTYPE == NMSA_BF16) ? bf16_to_f32(h) : f16_to_f32(h);
-}
-template <int DTYPE>
-__device__ __forceinline__ void st1(void* base, size_t off, float v)
-{
-    if (DTYPE == NMSA_F32) ((float*)base)[off] = v;
-    else ((uint16_t*)base)[off] = (DTYPE == NMSA_BF16) ? f32_to_bf16(v) : f32_to_f16(v);
-}
-
 template <int DTYPE, bool BWD>
 __global__ __launch_bounds__(LOSS_THREADS) void k_cos_emb(
     const void* __restrict__ pred, const int32_t* __restrict__ indices, const float* __restrict__ lut,
@@ -466,7 +452,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_cos_emb(
         float xy = 0.f, xx = 0.f, yy = 0.f;
         if (on) {
             for (int d = 0; d < D; ++d) {
-                const float xv = ld1<DTYPE>(pred, ((size_t)b * D + d) * P + p);
+                const float xv = ld_at<DTYPE>(pred, ((size_t)b * D + d) * P + p);
                 const float yv = y[d];
                 xy = fmaf(xv, yv, xy); xx = fmaf(xv, xv, xx); yy = fmaf(yv, yv, yy);
             }
@@ -480,8 +466,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_cos_emb(
             const float k2 = on ? g * xy / ((xx + EPS) * den) : 0.f;
             for (int d = 0; d < D; ++d) {
                 const size_t off = ((size_t)b * D + d) * P + p;
-                const float xv = on ? ld1<DTYPE>(pred, off) : 0.f;
-                st1<DTYPE>(grad, off, on ? fmaf(k2, xv, k1 * y[d]) : 0.f);
+                const float xv = on ? ld_at<DTYPE>(pred, off) : 0.f;
+                st_at<DTYPE>(grad, off, on ? fmaf(k2, xv, k1 * y[d]) : 0.f);
             }
         }
     }

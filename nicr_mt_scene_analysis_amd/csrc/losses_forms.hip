@@ -13,20 +13,6 @@
 namespace nmsa {
 namespace {
 
-template <int DTYPE>
-__device__ __forceinline__ float ldf(const void* base, size_t i)
-{
-    if (DTYPE == NMSA_F32) return ((const float*)base)[i];
-    const uint16_t h = ((const uint16_t*)base)[i];
-    return (DTYPE == NMSA_BF16) ? bf16_to_f32(h) : f16_to_f32(h);
-}
-template <int DTYPE>
-__device__ __forceinline__ void stf(void* base, size_t i, float v)
-{
-    if (DTYPE == NMSA_F32) ((float*)base)[i] = v;
-    else ((uint16_t*)base)[i] = (DTYPE == NMSA_BF16) ? f32_to_bf16(v) : f32_to_f16(v);
-}
-
 // out[i] = f(pred[i] - target[i]) (BWD: grad[i] = upstream[i] * f'(pred[i] - target[i])),
 // computed in fp32 and rounded once to the output's type, as ATen's op-math does
 template <int DTYPE, int ODT, int KIND, bool BWD>
@@ -36,11 +22,11 @@ __global__ __launch_bounds__(256) void k_elem_none(
 {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float d = ldf<DTYPE>(pred, i) - target[i];
-        if (!BWD) stf<ODT>(out, i, KIND == 0 ? d * d : fabsf(d));
+        const float d = ld_at<DTYPE>(pred, i) - target[i];
+        if (!BWD) st_at<ODT>(out, i, KIND == 0 ? d * d : fabsf(d));
         else {
             const float dd = KIND == 0 ? 2.0f * d : (float)((d > 0.f) - (d < 0.f));
-            stf<DTYPE>(out, i, ldf<ODT>(upstream, i) * dd);
+            st_at<DTYPE>(out, i, ld_at<ODT>(upstream, i) * dd);
         }
     }
 }
@@ -62,7 +48,7 @@ __global__ __launch_bounds__(256) void k_cos_rows(
         const size_t base = (size_t)r * D;
         float xy = 0.f, xx = 0.f, yy = 0.f;
         for (int d = lane; d < D; d += 64) {
-            const float xv = ldf<DTYPE>(x, base + d), yv = y[base + d];
+            const float xv = ld_at<DTYPE>(x, base + d), yv = y[base + d];
             xy = fmaf(xv, yv, xy); xx = fmaf(xv, xv, xx); yy = fmaf(yv, yv, yy);
         }
 #pragma unroll
@@ -82,7 +68,7 @@ __global__ __launch_bounds__(256) void k_cos_rows(
             const float g = s * upstream[(size_t)r * up_stride];
             const float k1 = g / den, k2 = -g * c / (xx + EPS);
             for (int d = lane; d < D; d += 64)
-                stf<DTYPE>(grad, base + d, fmaf(k2, ldf<DTYPE>(x, base + d), k1 * y[base + d]));
+                st_at<DTYPE>(grad, base + d, fmaf(k2, ld_at<DTYPE>(x, base + d), k1 * y[base + d]));
         }
     }
 }
@@ -96,14 +82,14 @@ __global__ __launch_bounds__(256) void k_vm_rows(
 {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += stride) {
-        const float x0 = ldf<DTYPE>(x, 2 * r), x1 = ldf<DTYPE>(x, 2 * r + 1);
+        const float x0 = ld_at<DTYPE>(x, 2 * r), x1 = ld_at<DTYPE>(x, 2 * r + 1);
         const float y0 = y[2 * r], y1 = y[2 * r + 1];
         const float e = __expf(kappa * (fmaf(x0, y0, x1 * y1) - 1.0f));
         if (!BWD) loss_rows[r] = 1.0f - e;
         else {
             const float g = -upstream[r] * kappa * e;
-            stf<DTYPE>(grad, 2 * r, g * y0);
-            stf<DTYPE>(grad, 2 * r + 1, g * y1);
+            st_at<DTYPE>(grad, 2 * r, g * y0);
+            st_at<DTYPE>(grad, 2 * r + 1, g * y1);
         }
     }
 }

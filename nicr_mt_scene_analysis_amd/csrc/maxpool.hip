@@ -28,7 +28,7 @@
 // element-aligned pointer.  Both routes give the same bits.
 // The grid is min(items, 8 workgroups per compute unit of nmsa_device_geometry), grid-stride.
 // Addressing: 64-bit plane base, 32-bit offsets inside a plane (H W < 2^31 is checked).
-#include "loss_common.hpp"
+#include "nmsa_common.hpp"
 
 namespace nmsa {
 namespace {
@@ -38,34 +38,12 @@ constexpr int MP_TILE_H = 8;             // output rows a lane walks
 constexpr int MP_BLOCKS_PER_CU = 8;
 constexpr uint32_t MP_NO_CODE = 255u;    // a window outside the map: matches no position
 
-template <typename T, int N>
-struct alignas(sizeof(T) * N > 16 ? 16 : sizeof(T) * N) mp_pack {
-    T v[N];
-};
-
-template <int DTYPE> struct mp_elem { typedef uint16_t type; };
-template <> struct mp_elem<NMSA_F32> { typedef float type; };
-
-template <int DTYPE>
-__device__ __forceinline__ float mp_ld(typename mp_elem<DTYPE>::type v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
-    else return f16_to_f32(v);
-}
-
-template <int DTYPE>
-__device__ __forceinline__ typename mp_elem<DTYPE>::type mp_st(float v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
-    else return f32_to_f16(v);
-}
+// elem, ld, st, pack: nmsa_common.hpp
 
 // the element p[0].  VEC: p is 4-byte aligned and p[1] lies inside the row, a half comes as the low part of
 // one dword
 template <int DTYPE, bool VEC>
-__device__ __forceinline__ typename mp_elem<DTYPE>::type mp_first(const typename mp_elem<DTYPE>::type* p)
+__device__ __forceinline__ typename elem<DTYPE>::type mp_first(const typename elem<DTYPE>::type* p)
 {
     if constexpr (VEC && DTYPE != NMSA_F32) return (uint16_t)(*(const uint32_t*)p & 0xffffu);
     else return p[0];
@@ -74,7 +52,7 @@ __device__ __forceinline__ typename mp_elem<DTYPE>::type mp_first(const typename
 // the element p[-1].  VEC: p is 4-byte aligned and p[-2] lies inside the row, a half comes as the high part
 // of one dword
 template <int DTYPE, bool VEC>
-__device__ __forceinline__ typename mp_elem<DTYPE>::type mp_before(const typename mp_elem<DTYPE>::type* p)
+__device__ __forceinline__ typename elem<DTYPE>::type mp_before(const typename elem<DTYPE>::type* p)
 {
     if constexpr (VEC && DTYPE != NMSA_F32) return (uint16_t)(*(const uint32_t*)(p - 2) >> 16);
     else return p[-1];
@@ -109,15 +87,15 @@ __device__ __forceinline__ void mp_take(mp_sel<S>& m, float v, S b, uint32_t k)
 // input row r (inside the map) scanned for the NO output pixels from ox0: the winner of the columns
 // 2 ox - 1, 2 ox, 2 ox + 1 that lie inside the map, k = its column position 0..2
 template <int DTYPE, int NO, bool VEC>
-__device__ __forceinline__ void mp_scan_row(const typename mp_elem<DTYPE>::type* xp, uint32_t r, const MpGeom& g,
-                                            uint32_t ox0, mp_sel<typename mp_elem<DTYPE>::type>* out)
+__device__ __forceinline__ void mp_scan_row(const typename elem<DTYPE>::type* xp, uint32_t r, const MpGeom& g,
+                                            uint32_t ox0, mp_sel<typename elem<DTYPE>::type>* out)
 {
-    typedef typename mp_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     const S* p = xp + r * g.W + 2 * ox0;
     S a[2 * NO + 1];                         // a[0]: column 2 ox0 - 1
     const bool left = ox0 > 0;
     if constexpr (VEC) {
-        const mp_pack<S, 2 * NO> v = *(const mp_pack<S, 2 * NO>*)p;
+        const pack<S, 2 * NO> v = *(const pack<S, 2 * NO>*)p;
 #pragma unroll
         for (int j = 0; j < 2 * NO; ++j) a[j + 1] = v.v[j];
         a[0] = left ? mp_before<DTYPE, true>(p) : a[1];
@@ -131,22 +109,22 @@ __device__ __forceinline__ void mp_scan_row(const typename mp_elem<DTYPE>::type*
     for (int j = 0; j < NO; ++j) {
         mp_sel<S> m;
         if (j == 0 && !left) {
-            m.v = mp_ld<DTYPE>(a[1]); m.b = a[1]; m.k = 1u;
+            m.v = ld<DTYPE>(a[1]); m.b = a[1]; m.k = 1u;
         } else {
-            m.v = mp_ld<DTYPE>(a[2 * j]); m.b = a[2 * j]; m.k = 0u;
-            mp_take(m, mp_ld<DTYPE>(a[2 * j + 1]), a[2 * j + 1], 1u);
+            m.v = ld<DTYPE>(a[2 * j]); m.b = a[2 * j]; m.k = 0u;
+            mp_take(m, ld<DTYPE>(a[2 * j + 1]), a[2 * j + 1], 1u);
         }
-        if (right) mp_take(m, mp_ld<DTYPE>(a[2 * j + 2]), a[2 * j + 2], 2u);
+        if (right) mp_take(m, ld<DTYPE>(a[2 * j + 2]), a[2 * j + 2], 2u);
         out[j] = m;
     }
 }
 
 template <int DTYPE, int NO>
 __global__ __launch_bounds__(MP_THREADS) void k_mp_fwd(
-    const typename mp_elem<DTYPE>::type* __restrict__ x, typename mp_elem<DTYPE>::type* __restrict__ y,
+    const typename elem<DTYPE>::type* __restrict__ x, typename elem<DTYPE>::type* __restrict__ y,
     uint8_t* __restrict__ code, const MpGeom g)
 {
-    typedef typename mp_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr bool VEC = NO > 1;
     for (uint32_t item = blockIdx.x; item < g.items; item += gridDim.x) {
         const uint32_t gu = item * MP_THREADS + threadIdx.x;
@@ -167,8 +145,8 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_fwd(
             mp_scan_row<DTYPE, NO, VEC>(xp, 2 * oy, g, ox0, mid);
             const bool below = 2 * oy + 1 < g.H;
             if (below) mp_scan_row<DTYPE, NO, VEC>(xp, 2 * oy + 1, g, ox0, next);
-            mp_pack<S, NO> yv;
-            mp_pack<uint8_t, NO> kv;
+            pack<S, NO> yv;
+            pack<uint8_t, NO> kv;
 #pragma unroll
             for (int j = 0; j < NO; ++j) {
                 mp_sel<S> m;
@@ -184,8 +162,8 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_fwd(
                 kv.v[j] = (uint8_t)m.k;
             }
             const uint32_t o = oy * g.Wo + ox0;
-            *(mp_pack<S, NO>*)(y + obase + o) = yv;
-            if (code) *(mp_pack<uint8_t, NO>*)(code + obase + o) = kv;
+            *(pack<S, NO>*)(y + obase + o) = yv;
+            if (code) *(pack<uint8_t, NO>*)(code + obase + o) = kv;
 #pragma unroll
             for (int j = 0; j < NO; ++j) prev[j] = next[j];
         }
@@ -195,24 +173,24 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_fwd(
 // window row oy for the outputs ox0 .. ox0 + NO (the last one: the right neighbour's first): gy and code;
 // MP_NO_CODE where the window lies outside the map
 template <int DTYPE, int NO, bool VEC>
-__device__ __forceinline__ void mp_gy_row(const typename mp_elem<DTYPE>::type* gp, const uint8_t* cp, uint32_t oy,
+__device__ __forceinline__ void mp_gy_row(const typename elem<DTYPE>::type* gp, const uint8_t* cp, uint32_t oy,
                                           const MpGeom& g, uint32_t ox0, float* gv, uint32_t* cd)
 {
-    typedef typename mp_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     if (oy >= g.Ho) {
 #pragma unroll
         for (int j = 0; j <= NO; ++j) { gv[j] = 0.0f; cd[j] = MP_NO_CODE; }
         return;
     }
     const uint32_t o = oy * g.Wo + ox0;
-    const mp_pack<S, NO> gvec = *(const mp_pack<S, NO>*)(gp + o);
-    const mp_pack<uint8_t, NO> cvec = *(const mp_pack<uint8_t, NO>*)(cp + o);
+    const pack<S, NO> gvec = *(const pack<S, NO>*)(gp + o);
+    const pack<uint8_t, NO> cvec = *(const pack<uint8_t, NO>*)(cp + o);
 #pragma unroll
-    for (int j = 0; j < NO; ++j) { gv[j] = mp_ld<DTYPE>(gvec.v[j]); cd[j] = cvec.v[j]; }
+    for (int j = 0; j < NO; ++j) { gv[j] = ld<DTYPE>(gvec.v[j]); cd[j] = cvec.v[j]; }
     if (ox0 + NO < g.Wo) {
-        gv[NO] = mp_ld<DTYPE>(mp_first<DTYPE, VEC>(gp + o + NO));
+        gv[NO] = ld<DTYPE>(mp_first<DTYPE, VEC>(gp + o + NO));
         // Wo is a multiple of NO on the vector route: the pair (quad) behind the lane's codes lies inside the row
-        if constexpr (VEC) cd[NO] = (uint32_t)(*(const mp_pack<uint8_t, NO>*)(cp + o + NO)).v[0];
+        if constexpr (VEC) cd[NO] = (uint32_t)(*(const pack<uint8_t, NO>*)(cp + o + NO)).v[0];
         else cd[NO] = cp[o + NO];
     } else {
         gv[NO] = 0.0f; cd[NO] = MP_NO_CODE;
@@ -233,26 +211,26 @@ __device__ __forceinline__ void mp_gather(float* acc, const float* gv, const uin
 }
 
 template <int DTYPE, int NO>
-__device__ __forceinline__ void mp_gx_store(typename mp_elem<DTYPE>::type* p, const float* acc, bool second)
+__device__ __forceinline__ void mp_gx_store(typename elem<DTYPE>::type* p, const float* acc, bool second)
 {
-    typedef typename mp_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     if constexpr (NO > 1) {
-        mp_pack<S, 2 * NO> v;
+        pack<S, 2 * NO> v;
 #pragma unroll
-        for (int j = 0; j < 2 * NO; ++j) v.v[j] = mp_st<DTYPE>(acc[j]);
-        *(mp_pack<S, 2 * NO>*)p = v;
+        for (int j = 0; j < 2 * NO; ++j) v.v[j] = st<DTYPE>(acc[j]);
+        *(pack<S, 2 * NO>*)p = v;
     } else {
-        p[0] = mp_st<DTYPE>(acc[0]);
-        if (second) p[1] = mp_st<DTYPE>(acc[1]);
+        p[0] = st<DTYPE>(acc[0]);
+        if (second) p[1] = st<DTYPE>(acc[1]);
     }
 }
 
 template <int DTYPE, int NO>
 __global__ __launch_bounds__(MP_THREADS) void k_mp_bwd(
-    const typename mp_elem<DTYPE>::type* __restrict__ gy, const uint8_t* __restrict__ code,
-    typename mp_elem<DTYPE>::type* __restrict__ gx, const MpGeom g)
+    const typename elem<DTYPE>::type* __restrict__ gy, const uint8_t* __restrict__ code,
+    typename elem<DTYPE>::type* __restrict__ gx, const MpGeom g)
 {
-    typedef typename mp_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     constexpr bool VEC = NO > 1;
     for (uint32_t item = blockIdx.x; item < g.items; item += gridDim.x) {
         const uint32_t gu = item * MP_THREADS + threadIdx.x;
@@ -288,7 +266,6 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_bwd(
     }
 }
 
-int mp_elem_bytes(int dtype) { return dtype == NMSA_F32 ? 4 : 2; }
 int mp_run(int dtype) { return dtype == NMSA_F32 ? 2 : 4; }          // output pixels of a lane, vector route
 
 // sizes every entry point checks; NMSA_OK, NMSA_ERR_ARG or NMSA_ERR_UNSUPPORTED
@@ -316,19 +293,11 @@ bool mp_geometry(int B, int C, int H, int W, int NO, MpGeom& g)
     return true;
 }
 
-bool mp_aligned(const void* p, uintptr_t n) { return (uintptr_t)p % n == 0; }
-
 // THE route rule: the vector route needs the lane's input run to divide the width and every tensor of the
 // call on 16 bytes
 bool mp_vector(int dtype, int W, const void* a, const void* b, const void* c)
 {
-    return W % (2 * mp_run(dtype)) == 0 && mp_aligned(a, 16) && mp_aligned(b, 16) && mp_aligned(c, 16);
-}
-
-unsigned mp_grid(const MpGeom& g)
-{
-    const uint64_t cap = (uint64_t)device_geometry().cus * MP_BLOCKS_PER_CU;
-    return (unsigned)(g.items < cap ? g.items : cap);
+    return W % (2 * mp_run(dtype)) == 0 && aligned(a, 16) && aligned(b, 16) && aligned(c, 16);
 }
 
 }  // namespace
@@ -339,8 +308,8 @@ extern "C" int nmsa_maxpool3x3s2_route(const void* x, const void* y_or_gx, int d
     using namespace nmsa;
     const int rc = mp_check_sizes(dtype, B, C, H, W);
     if (rc != NMSA_OK) return rc;
-    const uintptr_t e = (uintptr_t)mp_elem_bytes(dtype);
-    if (!x || !y_or_gx || !mp_aligned(x, e) || !mp_aligned(y_or_gx, e)) return NMSA_ERR_ARG;
+    const uintptr_t e = (uintptr_t)elem_bytes(dtype);
+    if (!x || !y_or_gx || !aligned(x, e) || !aligned(y_or_gx, e)) return NMSA_ERR_ARG;
     return mp_vector(dtype, W, x, y_or_gx, nullptr) ? NMSA_MP_ROUTE_VECTOR : NMSA_MP_ROUTE_PIXEL;
 }
 
@@ -351,15 +320,15 @@ extern "C" int nmsa_maxpool3x3s2_fwd(const void* x, int dtype, int B, int C, int
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = mp_check_sizes(dtype, B, C, H, W);
     if (rc != NMSA_OK) return rc;
-    const uintptr_t e = (uintptr_t)mp_elem_bytes(dtype);
-    if (!x || !y || !mp_aligned(x, e) || !mp_aligned(y, e)) return NMSA_ERR_ARG;
+    const uintptr_t e = (uintptr_t)elem_bytes(dtype);
+    if (!x || !y || !aligned(x, e) || !aligned(y, e)) return NMSA_ERR_ARG;
     const bool vec = mp_vector(dtype, W, x, y, code);
     MpGeom g;
     if (!mp_geometry(B, C, H, W, vec ? mp_run(dtype) : 1, g)) return NMSA_ERR_UNSUPPORTED;
-    const dim3 grid(mp_grid(g)), block(MP_THREADS);
+    const dim3 grid(capped_grid(g.items, MP_BLOCKS_PER_CU)), block(MP_THREADS);
 #define MP_FWD(DT)                                                                                          \
     do {                                                                                                    \
-        typedef mp_elem<DT>::type S;                                                                        \
+        typedef elem<DT>::type S;                                                                           \
         if (vec) hipLaunchKernelGGL((k_mp_fwd<DT, (DT == NMSA_F32 ? 2 : 4)>), grid, block, 0, stream,       \
                                     (const S*)x, (S*)y, code, g);                                           \
         else hipLaunchKernelGGL((k_mp_fwd<DT, 1>), grid, block, 0, stream, (const S*)x, (S*)y, code, g);    \
@@ -376,15 +345,15 @@ extern "C" int nmsa_maxpool3x3s2_bwd(const void* gy, const uint8_t* code, int dt
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = mp_check_sizes(dtype, B, C, H, W);
     if (rc != NMSA_OK) return rc;
-    const uintptr_t e = (uintptr_t)mp_elem_bytes(dtype);
-    if (!gy || !code || !gx || !mp_aligned(gy, e) || !mp_aligned(gx, e)) return NMSA_ERR_ARG;
+    const uintptr_t e = (uintptr_t)elem_bytes(dtype);
+    if (!gy || !code || !gx || !aligned(gy, e) || !aligned(gx, e)) return NMSA_ERR_ARG;
     const bool vec = mp_vector(dtype, W, gy, code, gx);
     MpGeom g;
     if (!mp_geometry(B, C, H, W, vec ? mp_run(dtype) : 1, g)) return NMSA_ERR_UNSUPPORTED;
-    const dim3 grid(mp_grid(g)), block(MP_THREADS);
+    const dim3 grid(capped_grid(g.items, MP_BLOCKS_PER_CU)), block(MP_THREADS);
 #define MP_BWD(DT)                                                                                          \
     do {                                                                                                    \
-        typedef mp_elem<DT>::type S;                                                                        \
+        typedef elem<DT>::type S;                                                                           \
         if (vec) hipLaunchKernelGGL((k_mp_bwd<DT, (DT == NMSA_F32 ? 2 : 4)>), grid, block, 0, stream,       \
                                     (const S*)gy, code, (S*)gx, g);                                         \
         else hipLaunchKernelGGL((k_mp_bwd<DT, 1>), grid, block, 0, stream, (const S*)gy, code, (S*)gx, g);  \

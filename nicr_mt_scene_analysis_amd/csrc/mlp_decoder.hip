@@ -8,8 +8,9 @@
 //   y_i [B, c_i, H >> s_i, W >> s_i], factor f_i = 1 << s_i; nearest or bilinear (align_corners = False)
 //   gy_i[b, c, p, q] = sum_{Y reads p} wy(Y, p) * ( sum_{X reads q} wx(X, q) * g_out[b, off_i + c, Y, X] )
 //
-// The arithmetic is that of nmsa_ppm_upcat_fwd / _bwd (context_module.hip), restated here: ATen's
-// float index arithmetic with scale = float(h) / float(H) (1 / f, exact), the blend
+// The arithmetic is that of nmsa_ppm_upcat_fwd / _bwd (context_module.hip), through the same
+// nearest_src, bilinear_src and bilerp of crop_resize.hpp: ATen's float index arithmetic with
+// scale = float(h) / float(H) (1 / f, exact), the blend
 // (a*wx0 + b*wx1)*wy0 + (c*wx0 + d*wx1)*wy1 with one fused multiply-add per sum; backward a row's
 // contributions left to right as fused multiply-adds from 0, the weighted row sums top to bottom as
 // fused multiply-adds from 0.  A branch with s_i == 0 is copied element for element.  No atomics, no
@@ -31,7 +32,6 @@
 // Grids: min(items, MLD_BLOCKS_PER_CU workgroups per compute unit of nmsa_device_geometry), grid-stride.
 // Addressing: 64-bit plane bases, 32-bit offsets inside a plane (H, W <= 32768 is checked).
 #include "crop_resize.hpp"
-#include "loss_common.hpp"
 
 namespace nmsa {
 namespace {
@@ -41,27 +41,7 @@ constexpr int MLD_BLOCKS_PER_CU = 8;
 constexpr int MLD_MAX_DIM = 32768;
 constexpr int MLD_MAX_SHIFT = 4;
 
-template <int DTYPE> struct mld_elem { typedef uint16_t type; };
-template <> struct mld_elem<NMSA_F32> { typedef float type; };
-
-template <int DTYPE>
-__device__ __forceinline__ float mld_ld(typename mld_elem<DTYPE>::type v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
-    else return f16_to_f32(v);
-}
-
-template <int DTYPE>
-__device__ __forceinline__ typename mld_elem<DTYPE>::type mld_st(float v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
-    else return f32_to_f16(v);
-}
-
-// VEC elements moved by one access (16 bytes on the vector route)
-template <typename S, int VEC> struct alignas(sizeof(S) * VEC) mld_pack { S v[VEC]; };
+// elem, ld, st, pack: nmsa_common.hpp; nearest_src, bilinear_src, bilerp: crop_resize.hpp
 
 struct MldDesc {
     uint32_t B, H, W, HW;
@@ -74,27 +54,6 @@ struct MldDesc {
     void* p[NMSA_MLPDEC_MAX_BRANCHES];
 };
 
-// ATen's bilinear source (area_pixel_compute_source_index, align_corners = False): the operations of
-// ppm_bilinear_src in context_module.hip in the same order
-__device__ __forceinline__ void mld_bilinear_src(float scale, int dst, int in,
-                                                 int& i0, int& i1, float& w0, float& w1)
-{
-    float s = __fmaf_rn(scale, __fadd_rn((float)dst, 0.5f), -0.5f);
-    s = (s < 0.f) ? 0.f : s;
-    i0 = min((int)s, in - 1);
-    i1 = min(i0 + 1, in - 1);
-    w1 = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
-    w0 = __fsub_rn(1.0f, w1);
-}
-
-__device__ __forceinline__ float mld_bilerp(float a, float b, float c, float d,
-                                            float wx0, float wx1, float wy0, float wy1)
-{
-    const float t0 = __fmaf_rn(a, wx0, __fmul_rn(b, wx1));
-    const float t1 = __fmaf_rn(c, wx0, __fmul_rn(d, wx1));
-    return __fmaf_rn(t0, wy0, __fmul_rn(t1, wy1));
-}
-
 // the weight with which output index `dst` reads source cell `cell` (false: it does not read it)
 __device__ __forceinline__ bool mld_reads(int mode, float scale, int dst, int in, int cell, float& wgt)
 {
@@ -104,7 +63,7 @@ __device__ __forceinline__ bool mld_reads(int mode, float scale, int dst, int in
     }
     int i0, i1;
     float w0, w1;
-    mld_bilinear_src(scale, dst, in, i0, i1, w0, w1);
+    bilinear_src(scale, dst, in, i0, i1, w0, w1);
     wgt = __fadd_rn(i0 == cell ? w0 : 0.0f, i1 == cell ? w1 : 0.0f);
     return i0 == cell || i1 == cell;
 }
@@ -129,10 +88,10 @@ __device__ __forceinline__ void mld_readers(int mode, int sh, int out, int cell,
 // ------------------------------------------------------------------- upsample + concat forward
 template <int DTYPE, int VEC>
 __global__ __launch_bounds__(MLD_THREADS) void k_mlpdec_upcat_fwd(
-    typename mld_elem<DTYPE>::type* __restrict__ out, const MldDesc d, const uint32_t chunks, const uint32_t items)
+    typename elem<DTYPE>::type* __restrict__ out, const MldDesc d, const uint32_t chunks, const uint32_t items)
 {
-    typedef typename mld_elem<DTYPE>::type S;
-    typedef mld_pack<S, VEC> P;
+    typedef typename elem<DTYPE>::type S;
+    typedef pack<S, VEC> P;
     const int H = (int)d.H, W = (int)d.W;
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint32_t plane = item / chunks, chunk = item - plane * chunks;
@@ -171,17 +130,17 @@ __global__ __launch_bounds__(MLD_THREADS) void k_mlpdec_upcat_fwd(
         } else {
             int iy0, iy1;
             float wy0, wy1;
-            mld_bilinear_src(sy, h, ph, iy0, iy1, wy0, wy1);
+            bilinear_src(sy, h, ph, iy0, iy1, wy0, wy1);
             const S* r0 = src + iy0 * pw;
             const S* r1 = src + iy1 * pw;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 int ix0, ix1;
                 float wx0, wx1;
-                mld_bilinear_src(sx, w + k, pw, ix0, ix1, wx0, wx1);
-                r.v[k] = mld_st<DTYPE>(mld_bilerp(mld_ld<DTYPE>(r0[ix0]), mld_ld<DTYPE>(r0[ix1]),
-                                                  mld_ld<DTYPE>(r1[ix0]), mld_ld<DTYPE>(r1[ix1]),
-                                                  wx0, wx1, wy0, wy1));
+                bilinear_src(sx, w + k, pw, ix0, ix1, wx0, wx1);
+                r.v[k] = st<DTYPE>(bilerp(ld<DTYPE>(r0[ix0]), ld<DTYPE>(r0[ix1]),
+                                          ld<DTYPE>(r1[ix0]), ld<DTYPE>(r1[ix1]),
+                                          wx0, wx1, wy0, wy1));
             }
         }
         *(P*)op = r;
@@ -191,9 +150,9 @@ __global__ __launch_bounds__(MLD_THREADS) void k_mlpdec_upcat_fwd(
 // ------------------------------------------------------------------ upsample + concat backward
 template <int DTYPE>
 __global__ __launch_bounds__(MLD_THREADS) void k_mlpdec_upcat_bwd(
-    const typename mld_elem<DTYPE>::type* __restrict__ g_out, const MldDesc d, const uint32_t items)
+    const typename elem<DTYPE>::type* __restrict__ g_out, const MldDesc d, const uint32_t items)
 {
-    typedef typename mld_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     const int H = (int)d.H, W = (int)d.W;
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
         // the last branch whose first item is not behind `item` (a branch without items shares its
@@ -228,17 +187,15 @@ __global__ __launch_bounds__(MLD_THREADS) void k_mlpdec_upcat_bwd(
             float acc = 0.0f;
             for (int w = w0; w <= w1; ++w) {
                 float wx;
-                if (mld_reads(d.mode, sx, w, pw, q, wx)) acc = __fmaf_rn(mld_ld<DTYPE>(row[w]), wx, acc);
+                if (mld_reads(d.mode, sx, w, pw, q, wx)) acc = __fmaf_rn(ld<DTYPE>(row[w]), wx, acc);
             }
             s = __fmaf_rn(acc, wy, s);
         }
-        dst[plane * hw + pix] = mld_st<DTYPE>(s);
+        dst[plane * hw + pix] = st<DTYPE>(s);
     }
 }
 
 // ------------------------------------------------------------------------------------ host side
-bool mld_aligned(const void* p, int dtype) { return (uintptr_t)p % (dtype == NMSA_F32 ? 4u : 2u) == 0; }
-bool mld_on16(const void* p) { return (uintptr_t)p % 16u == 0; }
 int mld_vec(int dtype) { return dtype == NMSA_F32 ? 4 : 8; }
 
 // what every entry point checks of the sizes; NMSA_OK, NMSA_ERR_ARG or NMSA_ERR_UNSUPPORTED.  `c` may
@@ -267,9 +224,9 @@ int mld_check_sizes(int dtype, int mode, int B, int H, int W, int n, const int* 
 // THE route rule of the forward kernel
 bool mld_vector(const void* const* ys, const void* out, int dtype, int W, int n)
 {
-    if (W % mld_vec(dtype) || !mld_on16(out)) return false;
+    if (W % mld_vec(dtype) || !aligned(out, 16)) return false;
     for (int i = 0; i < n; ++i)
-        if (!mld_on16(ys[i])) return false;
+        if (!aligned(ys[i], 16)) return false;
     return true;
 }
 
@@ -287,12 +244,6 @@ void mld_desc(MldDesc& d, int B, int H, int W, int n, const int* c, const int* s
     }
 }
 
-unsigned mld_grid(uint64_t items)
-{
-    const uint64_t cap = (uint64_t)device_geometry().cus * MLD_BLOCKS_PER_CU;
-    return (unsigned)(items < cap ? items : cap);
-}
-
 }  // namespace
 }  // namespace nmsa
 
@@ -303,9 +254,9 @@ extern "C" int nmsa_mlpdec_route(const void* const* ys, const void* out, int dty
     int64_t c_total = 0;
     const int rc = mld_check_sizes(dtype, NMSA_MLPDEC_NEAREST, 1, H, W, n, nullptr, false, s, c_total);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!ys || !out || !mld_aligned(out, dtype)) return NMSA_ERR_ARG;
+    if (!ys || !out || !elem_aligned(out, dtype)) return NMSA_ERR_ARG;
     for (int i = 0; i < n; ++i)
-        if (!ys[i] || !mld_aligned(ys[i], dtype)) return NMSA_ERR_ARG;
+        if (!ys[i] || !elem_aligned(ys[i], dtype)) return NMSA_ERR_ARG;
     if (rc != NMSA_OK) return rc;
     return mld_vector(ys, out, dtype, W, n) ? NMSA_MLPDEC_ROUTE_VECTOR : NMSA_MLPDEC_ROUTE_ELEMENT;
 }
@@ -318,9 +269,9 @@ extern "C" int nmsa_mlpdec_upcat_fwd(const void* const* ys, int dtype, int B, in
     int64_t c_total = 0;
     const int rc = mld_check_sizes(dtype, mode, B, H, W, n, c, true, s, c_total);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!ys || !out || !mld_aligned(out, dtype)) return NMSA_ERR_ARG;
+    if (!ys || !out || !elem_aligned(out, dtype)) return NMSA_ERR_ARG;
     for (int i = 0; i < n; ++i)
-        if (!ys[i] || !mld_aligned(ys[i], dtype)) return NMSA_ERR_ARG;
+        if (!ys[i] || !elem_aligned(ys[i], dtype)) return NMSA_ERR_ARG;
     if (rc != NMSA_OK) return rc;
     const bool vector = mld_vector(ys, out, dtype, W, n);
     const uint64_t run = (uint64_t)MLD_THREADS * (vector ? mld_vec(dtype) : 1);
@@ -329,10 +280,10 @@ extern "C" int nmsa_mlpdec_upcat_fwd(const void* const* ys, int dtype, int B, in
     if (items > 0x7fffffffull) return NMSA_ERR_UNSUPPORTED;
     MldDesc d;
     mld_desc(d, B, H, W, n, c, s, (void* const*)ys, mode, c_total);
-    const dim3 grid(mld_grid(items)), block(MLD_THREADS);
+    const dim3 grid(capped_grid(items, MLD_BLOCKS_PER_CU)), block(MLD_THREADS);
 #define MLD_UPCAT_FWD(DT)                                                                                   \
     do {                                                                                                    \
-        typedef mld_elem<DT>::type S;                                                                       \
+        typedef elem<DT>::type S;                                                                           \
         if (vector)                                                                                         \
             hipLaunchKernelGGL((k_mlpdec_upcat_fwd<DT, 16 / sizeof(S)>), grid, block, 0, stream, (S*)out, d, \
                                (uint32_t)chunks, (uint32_t)items);                                          \
@@ -353,10 +304,10 @@ extern "C" int nmsa_mlpdec_upcat_bwd(const void* g_out, int dtype, int B, int H,
     int64_t c_total = 0;
     const int rc = mld_check_sizes(dtype, mode, B, H, W, n, c, true, s, c_total);
     if (rc == NMSA_ERR_ARG) return rc;
-    if (!g_out || !gys || !mld_aligned(g_out, dtype)) return NMSA_ERR_ARG;
+    if (!g_out || !gys || !elem_aligned(g_out, dtype)) return NMSA_ERR_ARG;
     bool any = false;
     for (int i = 0; i < n; ++i) {
-        if (!mld_aligned(gys[i], dtype)) return NMSA_ERR_ARG;    // NULL: that gradient is not wanted
+        if (!elem_aligned(gys[i], dtype)) return NMSA_ERR_ARG;    // NULL: that gradient is not wanted
         any = any || gys[i];
     }
     if (rc != NMSA_OK) return rc;
@@ -374,9 +325,9 @@ extern "C" int nmsa_mlpdec_upcat_bwd(const void* g_out, int dtype, int B, int H,
     }
     if (items > 0x7fffffffull) return NMSA_ERR_UNSUPPORTED;
     if (!any || items == 0) return NMSA_OK;
-    const dim3 grid(mld_grid(items)), block(MLD_THREADS);
+    const dim3 grid(capped_grid(items, MLD_BLOCKS_PER_CU)), block(MLD_THREADS);
 #define MLD_UPCAT_BWD(DT)                                                                                   \
-    hipLaunchKernelGGL((k_mlpdec_upcat_bwd<DT>), grid, block, 0, stream, (const mld_elem<DT>::type*)g_out, d, \
+    hipLaunchKernelGGL((k_mlpdec_upcat_bwd<DT>), grid, block, 0, stream, (const elem<DT>::type*)g_out, d,   \
                        (uint32_t)items)
     NMSA_DISPATCH_DTYPE(dtype, MLD_UPCAT_BWD)
 #undef MLD_UPCAT_BWD

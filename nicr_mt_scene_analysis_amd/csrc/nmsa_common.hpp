@@ -4,9 +4,20 @@
 #include <stdint.h>
 #include "../../include/nmsa.h"
 
+// run CALL(<dtype constant>) for the runtime dtype code (host side)
+#define NMSA_DISPATCH_DTYPE(dtype, CALL)          \
+    switch (dtype) {                              \
+        case NMSA_F32: CALL(NMSA_F32); break;     \
+        case NMSA_BF16: CALL(NMSA_BF16); break;   \
+        case NMSA_F16: CALL(NMSA_F16); break;     \
+        default: return NMSA_ERR_ARG;             \
+    }
+
 namespace nmsa {
 
 constexpr int kWave = 64;  // CDNA wavefront
+
+typedef float f32x4_s __attribute__((ext_vector_type(4)));
 
 extern thread_local int g_last_hip_error;
 
@@ -59,6 +70,69 @@ __device__ __forceinline__ float bf16_to_f32(uint16_t v)
 __device__ __forceinline__ float f16_to_f32(uint16_t v)
 {
     return (float)__builtin_bit_cast(_Float16, v);
+}
+
+__device__ __forceinline__ uint16_t f32_to_bf16(float f)
+{
+    // round-to-nearest-even via the hardware conversion (keeps NaN a NaN)
+    return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+__device__ __forceinline__ uint16_t f32_to_f16(float f)
+{
+    return __builtin_bit_cast(uint16_t, (_Float16)f);
+}
+
+// The storage type of a dtype code, and its conversions from and to the float32 the kernels compute in.
+template <int DTYPE> struct elem { typedef uint16_t type; };
+template <> struct elem<NMSA_F32> { typedef float type; };
+
+template <int DTYPE>
+__device__ __forceinline__ float ld(typename elem<DTYPE>::type v)
+{
+    if constexpr (DTYPE == NMSA_F32) return v;
+    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
+    else return f16_to_f32(v);
+}
+
+template <int DTYPE>
+__device__ __forceinline__ typename elem<DTYPE>::type st(float v)
+{
+    if constexpr (DTYPE == NMSA_F32) return v;
+    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
+    else return f32_to_f16(v);
+}
+
+// N elements moved by one access of up to 16 bytes
+template <typename T, int N>
+struct alignas(sizeof(T) * N > 16 ? 16 : sizeof(T) * N) pack {
+    T v[N];
+};
+
+// element i of an untyped array as float32, and its store
+template <int DTYPE>
+__device__ __forceinline__ float ld_at(const void* p, size_t i)
+{
+    if (DTYPE == NMSA_F32) return ((const float*)p)[i];
+    const uint16_t h = ((const uint16_t*)p)[i];
+    return (DTYPE == NMSA_BF16) ? bf16_to_f32(h) : f16_to_f32(h);
+}
+template <int DTYPE>
+__device__ __forceinline__ void st_at(void* p, size_t i, float v)
+{
+    if (DTYPE == NMSA_F32) ((float*)p)[i] = v;
+    else ((uint16_t*)p)[i] = (DTYPE == NMSA_BF16) ? f32_to_bf16(v) : f32_to_f16(v);
+}
+
+// host side: what the entry points check of a pointer, and the grid of a grid-stride kernel
+inline bool aligned(const void* p, uintptr_t n) { return (uintptr_t)p % n == 0; }
+inline int elem_bytes(int dtype) { return dtype == NMSA_F32 ? 4 : 2; }
+inline bool elem_aligned(const void* p, int dtype) { return aligned(p, (uintptr_t)elem_bytes(dtype)); }
+
+// min(items, blocks_per_cu workgroups per compute unit of the current device)
+inline unsigned capped_grid(uint64_t items, int blocks_per_cu)
+{
+    const uint64_t cap = (uint64_t)device_geometry().cus * blocks_per_cu;
+    return (unsigned)(items < cap ? items : cap);
 }
 
 // Wave-aggregated histogram increment: lanes holding the same key are counted

@@ -65,14 +65,6 @@ __device__ __forceinline__ void ld4(const void* p, size_t i, int n, float v[4])
     }
 }
 
-template <int DTYPE>
-__device__ __forceinline__ float ld1(const void* p, size_t i)
-{
-    if (DTYPE == NMSA_F32) return ((const float*)p)[i];
-    const uint16_t h = ((const uint16_t*)p)[i];
-    return (DTYPE == NMSA_BF16) ? bf16_to_f32(h) : f16_to_f32(h);
-}
-
 // =================================================================================
 // valid mask of the ground-truth normals
 // =================================================================================
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(NRM_THREADS) void k_rmse(
             ld4<NMSA_F32, VEC>(target, plane * HW + p, n, t);
             if (RESIZED) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) q[j] = ld1<DTYPE>(pred, plane * src_plane + soff[j]);
+                for (int j = 0; j < 4; ++j) q[j] = ld_at<DTYPE>(pred, plane * src_plane + soff[j]);
             } else {
                 ld4<DTYPE, VEC>(pred, plane * HW + p, n, q);
             }

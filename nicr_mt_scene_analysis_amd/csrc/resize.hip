@@ -35,34 +35,8 @@
 namespace nmsa {
 namespace {
 
-// CropResize, nearest_src, bad_geometry, make_geometry: crop_resize.hpp (shared with normal.hip)
-
-__device__ __forceinline__ void bilinear_src(float scale, int dst, int in,
-                                             int& i0, int& i1, float& w0, float& w1)
-{
-    float s = __fmaf_rn(scale, __fadd_rn((float)dst, 0.5f), -0.5f);
-    s = (s < 0.f) ? 0.f : s;
-    i0 = min((int)s, in - 1);
-    i1 = min(i0 + 1, in - 1);
-    w1 = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
-    w0 = __fsub_rn(1.0f, w1);
-}
-
-__device__ __forceinline__ float bilerp(float a, float b, float c, float d,
-                                        float wx0, float wx1, float wy0, float wy1)
-{
-    const float t0 = __fmaf_rn(a, wx0, __fmul_rn(b, wx1));
-    const float t1 = __fmaf_rn(c, wx0, __fmul_rn(d, wx1));
-    return __fmaf_rn(t0, wy0, __fmul_rn(t1, wy1));
-}
-
-template <int DTYPE>
-__device__ __forceinline__ float ld_elem(const void* p, size_t i)
-{
-    if (DTYPE == NMSA_F32) return ((const float*)p)[i];
-    const uint16_t h = ((const uint16_t*)p)[i];
-    return (DTYPE == NMSA_BF16) ? bf16_to_f32(h) : f16_to_f32(h);
-}
+// CropResize, nearest_src, bilinear_src, bilerp, bad_geometry, make_geometry: crop_resize.hpp; ld_at:
+// nmsa_common.hpp
 
 // the two horizontal neighbours (a = row[ix0], b = row[ix1]) with ONE load: ix1 == ix0 + 1
 // everywhere but on the clamped right edge, where both are the last pixel.  `xb` =
@@ -247,10 +221,10 @@ __global__ __launch_bounds__(256) void k_resize_bilinear(
                 ld_pair<DTYPE>(src, r0 + xo[j], edge[j], a[j], b[j]);
                 ld_pair<DTYPE>(src, r1 + xo[j], edge[j], c[j], d[j]);
             } else {
-                a[j] = ld_elem<DTYPE>(src, r0 + xo[j]);
-                b[j] = ld_elem<DTYPE>(src, r0 + xo1[j]);
-                c[j] = ld_elem<DTYPE>(src, r1 + xo[j]);
-                d[j] = ld_elem<DTYPE>(src, r1 + xo1[j]);
+                a[j] = ld_at<DTYPE>(src, r0 + xo[j]);
+                b[j] = ld_at<DTYPE>(src, r0 + xo1[j]);
+                c[j] = ld_at<DTYPE>(src, r1 + xo[j]);
+                d[j] = ld_at<DTYPE>(src, r1 + xo1[j]);
             }
         }
 #pragma unroll
@@ -316,10 +290,10 @@ __global__ __launch_bounds__(RZ_TW * RZ_TH) void k_argmax_resized(
                 ld_pair<DTYPE>(logits, pc + q0, edge, a[u], bb[u]);
                 ld_pair<DTYPE>(logits, pc + q1, edge, cc[u], d[u]);
             } else {
-                a[u] = ld_elem<DTYPE>(logits, pc + o00);
-                bb[u] = ld_elem<DTYPE>(logits, pc + o01);
-                cc[u] = ld_elem<DTYPE>(logits, pc + o10);
-                d[u] = ld_elem<DTYPE>(logits, pc + o11);
+                a[u] = ld_at<DTYPE>(logits, pc + o00);
+                bb[u] = ld_at<DTYPE>(logits, pc + o01);
+                cc[u] = ld_at<DTYPE>(logits, pc + o10);
+                d[u] = ld_at<DTYPE>(logits, pc + o11);
             }
         }
 #pragma unroll
@@ -330,8 +304,8 @@ __global__ __launch_bounds__(RZ_TW * RZ_TH) void k_argmax_resized(
     for (; c < C; ++c) {
         const size_t pc = (size_t)c * plane_stride;
         argmax_step<WITH_SCORE>(st, 0, round_to_storage<DTYPE>(bilerp(
-            ld_elem<DTYPE>(logits, pc + o00), ld_elem<DTYPE>(logits, pc + o01),
-            ld_elem<DTYPE>(logits, pc + o10), ld_elem<DTYPE>(logits, pc + o11),
+            ld_at<DTYPE>(logits, pc + o00), ld_at<DTYPE>(logits, pc + o01),
+            ld_at<DTYPE>(logits, pc + o10), ld_at<DTYPE>(logits, pc + o11),
             wx0, wx1, wy0, wy1)), c);
     }
     if (!valid) return;
@@ -418,31 +392,31 @@ __device__ __noinline__ float2 resized_column_exact(
     for (int c = 0; c < C; ++c) {
         const size_t pc = (size_t)c * plane_stride;
         const float v = round_to_storage<DTYPE>(bilerp(
-            ld_elem<DTYPE>(logits, pc + o00), ld_elem<DTYPE>(logits, pc + o01),
-            ld_elem<DTYPE>(logits, pc + o10), ld_elem<DTYPE>(logits, pc + o11),
+            ld_at<DTYPE>(logits, pc + o00), ld_at<DTYPE>(logits, pc + o01),
+            ld_at<DTYPE>(logits, pc + o10), ld_at<DTYPE>(logits, pc + o11),
             wx0, wx1, wy0, wy1));
         if (v != v || v == INFINITY) nan_or_pinf = true;
         if (fabsf(v) < INFINITY) any_finite = true;
         if (v > m) { m = v; am = c; }
     }
     if (nan_or_pinf || !any_finite) return make_float2(__int_as_float(0x7fc00000), __int_as_float(0));
-    auto ld = [&](int c) -> float {
+    auto col = [&](int c) -> float {
         const size_t pc = (size_t)c * plane_stride;
         return round_to_storage<DTYPE>(bilerp(
-            ld_elem<DTYPE>(logits, pc + o00), ld_elem<DTYPE>(logits, pc + o01),
-            ld_elem<DTYPE>(logits, pc + o10), ld_elem<DTYPE>(logits, pc + o11),
+            ld_at<DTYPE>(logits, pc + o00), ld_at<DTYPE>(logits, pc + o01),
+            ld_at<DTYPE>(logits, pc + o10), ld_at<DTYPE>(logits, pc + o11),
             wx0, wx1, wy0, wy1));
     };
     float se = 0.f;
     int first = am;           // lowest earlier class that may share the maximum's probability
     for (int c = 0; c < C; ++c) {
-        const float v = ld(c);
+        const float v = col(c);
         se += (v == -INFINITY) ? 0.f : __expf(v - m);
         if (c < first && __fsub_rn(v, m) >= TIE_CANDIDATE_GAP) first = c;
     }
     if (first >= am) return make_float2(1.0f / se, __int_as_float(am));
     float pm;                 // decided with the reference's own arithmetic (argmax_state.hpp)
-    const int cls = class_by_probability(ld, C, m, am, first, &pm);
+    const int cls = class_by_probability(col, C, m, am, first, &pm);
     return make_float2(pm, __int_as_float(cls));
 }
 

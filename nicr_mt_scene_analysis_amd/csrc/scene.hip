@@ -55,14 +55,6 @@ struct SceneArgs {
 };
 
 template <int DTYPE>
-__device__ __forceinline__ float ld_logit(const void* p, size_t i)
-{
-    if (DTYPE == NMSA_F32) return ((const float*)p)[i];
-    const uint16_t h = ((const uint16_t*)p)[i];
-    return (DTYPE == NMSA_BF16) ? bf16_to_f32(h) : f16_to_f32(h);
-}
-
-template <int DTYPE>
 __device__ __forceinline__ void st_grad(void* p, size_t i, double g)
 {
     const float f = (float)g;
@@ -144,7 +136,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_scene_step(SceneArgs a)
             float bv = -INFINITY;
             int bi = INT_MAX;
             for (int c = lane; c < C; c += kWave) {
-                const float x = ld_logit<DTYPE>(a.logits, base + c);
+                const float x = ld_at<DTYPE>(a.logits, base + c);
                 if (bi == INT_MAX || x > bv) { bv = x; bi = c; }
             }
 #pragma unroll
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_scene_step(SceneArgs a)
             // S = sum exp(x - m); with label smoothing also A = sum w[c] * x[c]
             double s = 0.0, wx = 0.0;
             for (int c = lane; c < C; c += kWave) {
-                const double x = (double)ld_logit<DTYPE>(a.logits, base + c);
+                const double x = (double)ld_at<DTYPE>(a.logits, base + c);
                 s += exp(x - m);
                 if (eps > 0.0) wx += (a.weights ? (double)a.weights[c] : 1.0) * x;
             }
@@ -187,7 +179,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_scene_step(SceneArgs a)
                 double term = 0.0;
                 if (valid) {
                     const double log_s = log(s);
-                    const double xt = (double)ld_logit<DTYPE>(a.logits, base + t);
+                    const double xt = (double)ld_at<DTYPE>(a.logits, base + t);
                     term = (1.0 - eps) * wt * (log_s + (m - xt));
                     if (eps > 0.0) term += eps_c * (W * (m + log_s) - wave_allreduce_sum(wx));
                 }
@@ -199,7 +191,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_scene_step(SceneArgs a)
                     // 0 - softmax * 0 through log_softmax's backward)
                     double g = poisoned ? (double)NAN : 0.0;
                     if (valid) {
-                        const double x = (double)ld_logit<DTYPE>(a.logits, base + c);
+                        const double x = (double)ld_at<DTYPE>(a.logits, base + c);
                         const double p = exp(x - m) / s;
                         const double wc = a.weights ? (double)a.weights[c] : 1.0;
                         g = ((1.0 - eps) * wt * (p - (c == t ? 1.0 : 0.0)) + eps_c * (W * p - wc)) / D;

@@ -25,14 +25,6 @@ constexpr int SC_THREADS = 256;
 constexpr int SC_PX_PER_THREAD = 4;
 constexpr int SC_PX_PER_BLOCK = SC_THREADS * SC_PX_PER_THREAD * 4;     // 4096 px per block
 
-template <int DTYPE>
-__device__ __forceinline__ float ld_logit(const void* p, size_t i)
-{
-    if (DTYPE == NMSA_F32) return ((const float*)p)[i];
-    const uint16_t h = ((const uint16_t*)p)[i];
-    return (DTYPE == NMSA_BF16) ? bf16_to_f32(h) : f16_to_f32(h);
-}
-
 __device__ __forceinline__ int64_t class_of(int64_t pan, int64_t mipc, int shift)
 {
     return shift >= 0 ? (pan >> shift) : (pan / mipc);
@@ -89,8 +81,8 @@ __global__ __launch_bounds__(SC_THREADS) void k_scores_semantic(
                 if (c == am[j]) {
                     s[j] = pm[j];
                 } else {
-                    const float xc = ld_logit<DTYPE>(logits, img_logits + (size_t)c * P + p0 + j);
-                    const float xm = ld_logit<DTYPE>(logits, img_logits + (size_t)am[j] * P + p0 + j);
+                    const float xc = ld_at<DTYPE>(logits, img_logits + (size_t)c * P + p0 + j);
+                    const float xm = ld_at<DTYPE>(logits, img_logits + (size_t)am[j] * P + p0 + j);
                     s[j] = __expf(xc - xm) * pm[j];
                 }
             }

@@ -33,7 +33,7 @@
 // and pointers off 16 bytes take NP = 1 with element-wise accesses (no alignment assumed).
 // The grid is min(items, 8 workgroups per compute unit of nmsa_device_geometry), grid-stride.
 // Addressing: 64-bit plane base, 32-bit offsets inside a plane (4hw < 2^31 is checked).
-#include "loss_common.hpp"
+#include "nmsa_common.hpp"
 
 namespace nmsa {
 namespace {
@@ -44,57 +44,35 @@ constexpr int UP_BLOCKS_PER_CU = 8;
 constexpr int UP_PARTIAL = 10;           // gW[3][3], gb
 constexpr int UP_REDUCE_THREADS = 64;
 
-template <typename T, int N>
-struct alignas(sizeof(T) * N > 16 ? 16 : sizeof(T) * N) up_pack {
-    T v[N];
-};
-
-template <int DTYPE> struct up_elem { typedef uint16_t type; };
-template <> struct up_elem<NMSA_F32> { typedef float type; };
-
-template <int DTYPE>
-__device__ __forceinline__ float up_ld(typename up_elem<DTYPE>::type v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return bf16_to_f32(v);
-    else return f16_to_f32(v);
-}
-
-template <int DTYPE>
-__device__ __forceinline__ typename up_elem<DTYPE>::type up_st(float v)
-{
-    if constexpr (DTYPE == NMSA_F32) return v;
-    else if constexpr (DTYPE == NMSA_BF16) return f32_to_bf16(v);
-    else return f32_to_f16(v);
-}
+// elem, ld, st, pack: nmsa_common.hpp
 
 // N elements from p: one vector access on the vector route, element-wise on the one-pixel route
 template <int DTYPE, int N, bool VEC>
-__device__ __forceinline__ void up_load(const typename up_elem<DTYPE>::type* p, float* out)
+__device__ __forceinline__ void up_load(const typename elem<DTYPE>::type* p, float* out)
 {
-    typedef typename up_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     if constexpr (VEC) {
-        const up_pack<S, N> v = *(const up_pack<S, N>*)p;
+        const pack<S, N> v = *(const pack<S, N>*)p;
 #pragma unroll
-        for (int j = 0; j < N; ++j) out[j] = up_ld<DTYPE>(v.v[j]);
+        for (int j = 0; j < N; ++j) out[j] = ld<DTYPE>(v.v[j]);
     } else {
 #pragma unroll
-        for (int j = 0; j < N; ++j) out[j] = up_ld<DTYPE>(p[j]);
+        for (int j = 0; j < N; ++j) out[j] = ld<DTYPE>(p[j]);
     }
 }
 
 template <int DTYPE, int N, bool VEC>
-__device__ __forceinline__ void up_store(typename up_elem<DTYPE>::type* p, const float* in)
+__device__ __forceinline__ void up_store(typename elem<DTYPE>::type* p, const float* in)
 {
-    typedef typename up_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     if constexpr (VEC) {
-        up_pack<S, N> v;
+        pack<S, N> v;
 #pragma unroll
-        for (int j = 0; j < N; ++j) v.v[j] = up_st<DTYPE>(in[j]);
-        *(up_pack<S, N>*)p = v;
+        for (int j = 0; j < N; ++j) v.v[j] = st<DTYPE>(in[j]);
+        *(pack<S, N>*)p = v;
     } else {
 #pragma unroll
-        for (int j = 0; j < N; ++j) p[j] = up_st<DTYPE>(in[j]);
+        for (int j = 0; j < N; ++j) p[j] = st<DTYPE>(in[j]);
     }
 }
 
@@ -109,7 +87,7 @@ struct UpGeom {
 
 // input row `r` of a plane (r may be -1 or h), columns s0-1 .. s0+NP, halo by the pad mode
 template <int DTYPE, int NP>
-__device__ __forceinline__ void up_x_row(const typename up_elem<DTYPE>::type* xp, int r, const UpGeom& g,
+__device__ __forceinline__ void up_x_row(const typename elem<DTYPE>::type* xp, int r, const UpGeom& g,
                                          uint32_t s0, float* a)
 {
     const bool outside = r < 0 || r >= (int)g.h;
@@ -119,18 +97,18 @@ __device__ __forceinline__ void up_x_row(const typename up_elem<DTYPE>::type* xp
         return;
     }
     const uint32_t rc = r < 0 ? 0u : (r >= (int)g.h ? g.h - 1 : (uint32_t)r);
-    const typename up_elem<DTYPE>::type* p = xp + rc * g.w + s0;
+    const typename elem<DTYPE>::type* p = xp + rc * g.w + s0;
     up_load<DTYPE, NP, (NP > 1)>(p, a + 1);
-    a[0] = s0 > 0 ? up_ld<DTYPE>(p[-1]) : (g.zeropad ? 0.0f : a[1]);
-    a[NP + 1] = s0 + NP < g.w ? up_ld<DTYPE>(p[NP]) : (g.zeropad ? 0.0f : a[NP]);
+    a[0] = s0 > 0 ? ld<DTYPE>(p[-1]) : (g.zeropad ? 0.0f : a[1]);
+    a[NP + 1] = s0 + NP < g.w ? ld<DTYPE>(p[NP]) : (g.zeropad ? 0.0f : a[NP]);
 }
 
 template <int DTYPE, int NP>
 __global__ __launch_bounds__(UP_THREADS) void k_up_fwd(
-    const typename up_elem<DTYPE>::type* __restrict__ x, const float* __restrict__ weight,
-    const float* __restrict__ bias, typename up_elem<DTYPE>::type* __restrict__ y, const UpGeom g)
+    const typename elem<DTYPE>::type* __restrict__ x, const float* __restrict__ weight,
+    const float* __restrict__ bias, typename elem<DTYPE>::type* __restrict__ y, const UpGeom g)
 {
-    typedef typename up_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     for (uint32_t item = blockIdx.x; item < g.items; item += gridDim.x) {
         const uint32_t plane = item / g.chunks, chunk = item - plane * g.chunks;
         const uint32_t unit = chunk * UP_THREADS + threadIdx.x;
@@ -191,7 +169,7 @@ __global__ __launch_bounds__(UP_THREADS) void k_up_fwd(
 
 // gy row Y of a plane (0 outside 0 .. 2h-1), columns 2*s0-1 .. 2*s0+2*NP (0 outside 0 .. 2w-1)
 template <int DTYPE, int NP>
-__device__ __forceinline__ void up_gy_row(const typename up_elem<DTYPE>::type* gp, int Y, const UpGeom& g,
+__device__ __forceinline__ void up_gy_row(const typename elem<DTYPE>::type* gp, int Y, const UpGeom& g,
                                           uint32_t s0, float* a)
 {
     if (Y < 0 || Y >= (int)(2 * g.h)) {
@@ -199,19 +177,19 @@ __device__ __forceinline__ void up_gy_row(const typename up_elem<DTYPE>::type* g
         for (int j = 0; j < 2 * NP + 2; ++j) a[j] = 0.0f;
         return;
     }
-    const typename up_elem<DTYPE>::type* p = gp + (uint32_t)Y * (2 * g.w) + 2 * s0;
+    const typename elem<DTYPE>::type* p = gp + (uint32_t)Y * (2 * g.w) + 2 * s0;
     up_load<DTYPE, 2 * NP, (NP > 1)>(p, a + 1);
-    a[0] = s0 > 0 ? up_ld<DTYPE>(p[-1]) : 0.0f;
-    a[2 * NP + 1] = s0 + NP < g.w ? up_ld<DTYPE>(p[2 * NP]) : 0.0f;
+    a[0] = s0 > 0 ? ld<DTYPE>(p[-1]) : 0.0f;
+    a[2 * NP + 1] = s0 + NP < g.w ? ld<DTYPE>(p[2 * NP]) : 0.0f;
 }
 
 template <int DTYPE, int NP>
 __global__ __launch_bounds__(UP_THREADS) void k_up_bwd(
-    const typename up_elem<DTYPE>::type* __restrict__ gy, const typename up_elem<DTYPE>::type* __restrict__ x,
-    const float* __restrict__ weight, typename up_elem<DTYPE>::type* __restrict__ gx,
+    const typename elem<DTYPE>::type* __restrict__ gy, const typename elem<DTYPE>::type* __restrict__ x,
+    const float* __restrict__ weight, typename elem<DTYPE>::type* __restrict__ gx,
     float* __restrict__ partials, const UpGeom g)
 {
-    typedef typename up_elem<DTYPE>::type S;
+    typedef typename elem<DTYPE>::type S;
     __shared__ float red[UP_THREADS / kWave][UP_PARTIAL];
     const bool rep = !g.zeropad;
     for (uint32_t item = blockIdx.x; item < g.items; item += gridDim.x) {
@@ -340,7 +318,6 @@ __global__ __launch_bounds__(UP_REDUCE_THREADS) void k_up_reduce(
     }
 }
 
-int up_elem_bytes(int dtype) { return dtype == NMSA_F32 ? 4 : 2; }
 int up_run(int dtype) { return dtype == NMSA_F32 ? 2 : 4; }
 
 // sizes every entry point checks; NMSA_OK, NMSA_ERR_ARG or NMSA_ERR_UNSUPPORTED
@@ -367,19 +344,11 @@ bool up_geometry(int B, int C, int h, int w, int NP, int zeropad, UpGeom& g)
     return true;
 }
 
-bool up_aligned(const void* p, uintptr_t n) { return (uintptr_t)p % n == 0; }
-
 // THE route rule: the vector route needs the lane run to divide the width and every tensor of
 // the call on 16 bytes
 bool up_vector(int dtype, int w, const void* a, const void* b, const void* c)
 {
-    return w % up_run(dtype) == 0 && up_aligned(a, 16) && up_aligned(b, 16) && up_aligned(c, 16);
-}
-
-unsigned up_grid(const UpGeom& g)
-{
-    const uint64_t cap = (uint64_t)device_geometry().cus * UP_BLOCKS_PER_CU;
-    return (unsigned)(g.items < cap ? g.items : cap);
+    return w % up_run(dtype) == 0 && aligned(a, 16) && aligned(b, 16) && aligned(c, 16);
 }
 
 }  // namespace
@@ -391,8 +360,8 @@ extern "C" int nmsa_upsample2x_dw3x3_route(const void* x, const void* y_or_gx, i
     using namespace nmsa;
     const int rc = up_check_sizes(dtype, B, C, h, w);
     if (rc != NMSA_OK) return rc == NMSA_ERR_UNSUPPORTED ? rc : NMSA_ERR_ARG;
-    const uintptr_t e = (uintptr_t)up_elem_bytes(dtype);
-    if (!x || !y_or_gx || !up_aligned(x, e) || !up_aligned(y_or_gx, e)) return NMSA_ERR_ARG;
+    const uintptr_t e = (uintptr_t)elem_bytes(dtype);
+    if (!x || !y_or_gx || !aligned(x, e) || !aligned(y_or_gx, e)) return NMSA_ERR_ARG;
     return up_vector(dtype, w, x, y_or_gx, nullptr) ? NMSA_UP_ROUTE_VECTOR : NMSA_UP_ROUTE_PIXEL;
 }
 
@@ -404,17 +373,17 @@ extern "C" int nmsa_upsample2x_dw3x3_fwd(const void* x, int dtype, const float* 
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = up_check_sizes(dtype, B, C, h, w);
     if (rc != NMSA_OK) return rc;
-    const uintptr_t e = (uintptr_t)up_elem_bytes(dtype);
+    const uintptr_t e = (uintptr_t)elem_bytes(dtype);
     if (!x || !weight || !y || (zeropad != 0 && zeropad != 1)) return NMSA_ERR_ARG;
-    if (!up_aligned(x, e) || !up_aligned(y, e) || !up_aligned(weight, 4) || !up_aligned(bias, 4))
+    if (!aligned(x, e) || !aligned(y, e) || !aligned(weight, 4) || !aligned(bias, 4))
         return NMSA_ERR_ARG;
     const bool vec = up_vector(dtype, w, x, y, nullptr);
     UpGeom g;
     if (!up_geometry(B, C, h, w, vec ? up_run(dtype) : 1, zeropad, g)) return NMSA_ERR_UNSUPPORTED;
-    const dim3 grid(up_grid(g)), block(UP_THREADS);
+    const dim3 grid(capped_grid(g.items, UP_BLOCKS_PER_CU)), block(UP_THREADS);
 #define UP_FWD(DT)                                                                                          \
     do {                                                                                                    \
-        typedef up_elem<DT>::type S;                                                                        \
+        typedef elem<DT>::type S;                                                                           \
         if (vec) hipLaunchKernelGGL((k_up_fwd<DT, (DT == NMSA_F32 ? 2 : 4)>), grid, block, 0, stream,       \
                                     (const S*)x, weight, bias, (S*)y, g);                                   \
         else hipLaunchKernelGGL((k_up_fwd<DT, 1>), grid, block, 0, stream, (const S*)x, weight, bias,       \
@@ -444,25 +413,25 @@ extern "C" int nmsa_upsample2x_dw3x3_bwd(const void* gy, const void* x, int dtyp
     hipStream_t stream = (hipStream_t)stream_;
     const int rc = up_check_sizes(dtype, B, C, h, w);
     if (rc != NMSA_OK) return rc;
-    const uintptr_t e = (uintptr_t)up_elem_bytes(dtype);
+    const uintptr_t e = (uintptr_t)elem_bytes(dtype);
     if (!gy || !x || !weight || (zeropad != 0 && zeropad != 1)) return NMSA_ERR_ARG;
-    if (!up_aligned(gy, e) || !up_aligned(x, e) || !up_aligned(gx, e) || !up_aligned(weight, 4) ||
-        !up_aligned(gweight, 4) || !up_aligned(gbias, 4))
+    if (!aligned(gy, e) || !aligned(x, e) || !aligned(gx, e) || !aligned(weight, 4) ||
+        !aligned(gweight, 4) || !aligned(gbias, 4))
         return NMSA_ERR_ARG;
     const bool reduce = gweight || gbias;
     const bool vec = up_vector(dtype, w, gy, x, gx);
     UpGeom g;
     if (!up_geometry(B, C, h, w, vec ? up_run(dtype) : 1, zeropad, g)) return NMSA_ERR_UNSUPPORTED;
     if (reduce) {
-        if (!workspace || !up_aligned(workspace, 16)) return NMSA_ERR_ARG;
+        if (!workspace || !aligned(workspace, 16)) return NMSA_ERR_ARG;
         if (workspace_bytes < (size_t)g.items * UP_PARTIAL * sizeof(float)) return NMSA_ERR_WORKSPACE;
     }
     if (!gx && !reduce) return NMSA_OK;
     float* partials = reduce ? (float*)workspace : nullptr;
-    const dim3 grid(up_grid(g)), block(UP_THREADS);
+    const dim3 grid(capped_grid(g.items, UP_BLOCKS_PER_CU)), block(UP_THREADS);
 #define UP_BWD(DT)                                                                                          \
     do {                                                                                                    \
-        typedef up_elem<DT>::type S;                                                                        \
+        typedef elem<DT>::type S;                                                                           \
         if (vec) hipLaunchKernelGGL((k_up_bwd<DT, (DT == NMSA_F32 ? 2 : 4)>), grid, block, 0, stream,       \
                                     (const S*)gy, (const S*)x, weight, (S*)gx, partials, g);                \
         else hipLaunchKernelGGL((k_up_bwd<DT, 1>), grid, block, 0, stream, (const S*)gy, (const S*)x,       \
