@@ -1530,6 +1530,58 @@ int nmsa_maxpool3x3s2_fwd(const void* x, int dtype, int B, int C, int H, int W, 
 int nmsa_maxpool3x3s2_bwd(const void* gy, const uint8_t* code, int dtype, int B, int C, int H, int W, void* gx,
                           nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * the scene classification decoder (csrc/scene_head.hip)
+ *     model/decoder/scene.py: adaptive_avg_pool2d(x, 1) -> flatten -> nn.Linear, the producer of the [B,K] logits
+ *     nmsa_scene_step consumes.
+ *
+ *   x, gx            [B,C,H,W]  NMSA_F32 | NMSA_BF16 | NMSA_F16 (dtype_x), contiguous
+ *   weight, gweight  f32 [K,C]
+ *   bias, gbias      f32 [K]; bias may be NULL (no bias is added)
+ *   pooled           f32 [B,C]; NULL in the forward call: not wanted (inference)
+ *   logits, g        [B,K] in dtype_out / dtype_g, any of the three, independent of dtype_x
+ *
+ * nmsa_scene_head_fwd: ONE launch (one workgroup per image), no workspace.  With V = 4 (f32) / 8 (half) the plane
+ *   of H W elements is cut into chunks of V consecutive elements (the last one short); chunk j belongs to lane
+ *   j % 64.  A lane adds the elements of its chunks in ascending order to a float32 0; the 64 lane sums are
+ *   combined by halves (v[l] += v[l + o] for o = 32, 16, 8, 4, 2, 1); pooled[b,c] = S / float(H W), IEEE
+ *   division.  H W == 1: pooled = x, converted, no division and no sum.  logits[b,k]: lane l starts from a
+ *   float32 0 and takes acc = fma(weight[k,c], pooled[b,c], acc) for c = l, l + 64, ..; the 64 lane sums are
+ *   combined by halves as above; then + bias[k] (one add, skipped for a NULL bias) and ONE rounding to dtype_out.
+ * nmsa_scene_head_bwd: ONE launch, no atomics, no workspace, no hand-off between workgroups; any of gx, gweight
+ *   and gbias may be NULL (not wanted; all three NULL: NMSA_OK after the checks, nothing is launched).
+ *     gs[b,c]      = fma(g[b,k], weight[k,c], gs) from a float32 0, k ascending
+ *     gx[b,c,:]    = gs[b,c] / float(H W) (H W == 1: gs[b,c]), rounded once to dtype_x, the whole plane written
+ *     gweight[k,c] = fma(g[b,k], pooled[b,c], acc) from a float32 0, b ascending
+ *     gbias[k]     = acc + g[b,k] from a float32 0, b ascending
+ *   g is converted to float32 exactly.  Every order above depends on (H W, C, K, B, dtypes) alone: two calls on the
+ *   same inputs give the same bits, on every route and with any grid.  The grid is at most 8 workgroups of 256
+ *   lanes per compute unit of nmsa_device_geometry and LOOPS over the rest of the items (a wave per plane — a
+ *   lane per plane when H W == 1 —, a lane per gweight element, a lane per gbias element).
+ * nmsa_scene_head_route (host only, nothing is launched, no device is touched): the route of a call whose map (x
+ *   in the forward, gx in the backward call) is `x_or_gx`.  NMSA_SH_ROUTE_UNIT: H W == 1.  NMSA_SH_ROUTE_VECTOR: a
+ *   chunk is one 16-byte access; taken when H W % 4 == 0 (f32) / H W % 8 == 0 (half) and the map starts on 16
+ *   bytes.  NMSA_SH_ROUTE_ELEMENT: element-wise accesses, any size and any element-aligned pointer.  All give the
+ *   same bits.
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a dtype other than
+ * the three, B, C, H, W or K below 1, a NULL x / weight / logits (forward), g / pooled / weight (backward) or map
+ * (route), a pointer that is not aligned to its element.  NMSA_ERR_UNSUPPORTED: C above
+ * NMSA_SCENE_HEAD_MAX_CHANNELS (pooled[b,:] is kept in the forward's LDS), K above NMSA_SCENE_MAX_CLASSES, a plane
+ * of 2^31 elements or more, 2^31 or more wave items (B C + ceil(K C / 64) + ceil(K / 64)).  No host
+ * synchronisation, no allocation; capturable in a hipGraph as a single chain.
+ * ------------------------------------------------------------------------- */
+#define NMSA_SCENE_HEAD_MAX_CHANNELS 2048
+#define NMSA_SH_ROUTE_UNIT 1
+#define NMSA_SH_ROUTE_VECTOR 2
+#define NMSA_SH_ROUTE_ELEMENT 4
+int nmsa_scene_head_route(const void* x_or_gx, int dtype_x, int B, int C, int H, int W, int K);
+int nmsa_scene_head_fwd(const void* x, int dtype_x, int B, int C, int H, int W, const float* weight,
+                        const float* bias, float* pooled, void* logits, int dtype_out, int K,
+                        nmsa_stream_t stream);
+int nmsa_scene_head_bwd(const void* g, int dtype_g, const float* pooled, const float* weight, int B, int C, int H,
+                        int W, int K, void* gx, int dtype_x, float* gweight, float* gbias, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

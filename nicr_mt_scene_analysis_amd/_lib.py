@@ -53,6 +53,9 @@ NMSA_BNTAIL_ROUTE_VECTOR, NMSA_BNTAIL_ROUTE_ELEMENT = 1, 2
 NMSA_BNTAIL_SEGMENT = 2048
 # include/nmsa.h: answers of nmsa_maxpool3x3s2_route
 NMSA_MP_ROUTE_VECTOR, NMSA_MP_ROUTE_PIXEL = 1, 2
+# include/nmsa.h: channel limit and route answers of the nmsa_scene_head_* entry points
+NMSA_SCENE_HEAD_MAX_CHANNELS = 2048
+NMSA_SH_ROUTE_UNIT, NMSA_SH_ROUTE_VECTOR, NMSA_SH_ROUTE_ELEMENT = 1, 2, 4
 
 
 class NmsaError(RuntimeError):
@@ -166,6 +169,9 @@ _SIGNATURES = {
     'nmsa_maxpool3x3s2_route': (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
     'nmsa_maxpool3x3s2_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'nmsa_maxpool3x3s2_bwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'nmsa_scene_head_route': (_i, [_vp, _i, _i, _i, _i, _i, _i]),
+    'nmsa_scene_head_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    'nmsa_scene_head_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

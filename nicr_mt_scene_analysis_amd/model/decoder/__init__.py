@@ -1,6 +1,7 @@
 """The MLP (SegFormer-style) decoders of the reference's model/decoder package; their resize +
-concatenation step runs on HIP (see mlp_base.py).  The convolutional dense decoders, the panoptic
-helper and the scene decoder are not part of this package."""
+concatenation step runs on HIP (see mlp_base.py), the scene classification decoder, whose global pool and
+linear head are one HIP launch (see scene.py), and the panoptic helper (plain torch).  The
+convolutional dense decoders are not part of this package."""
 from .base import DecoderBase
 from .dense_utils import create_task_head
 from .mlp_base import MLPDecoderBase
@@ -10,3 +11,6 @@ from .semantic import SemanticMLPDecoder
 from .instance import InstanceHead
 from .instance import InstanceMLPDecoder
 from .normal import NormalMLPDecoder
+from .scene import SceneClassificationDecoder
+from .scene import SceneHeadFunction
+from .panoptic import PanopticHelper

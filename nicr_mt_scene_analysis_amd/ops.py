@@ -2086,6 +2086,91 @@ def maxpool3x3s2_route(x: torch.Tensor, *others: torch.Tensor) -> int:
     return route
 
 
+# ------------------------------------------------------------- the scene classification decoder
+def _sh_params(weight: torch.Tensor, bias: Optional[torch.Tensor], C: int):
+    _require_on_device(weight, 'weight')
+    if weight.ndim != 2 or weight.dtype != torch.float32 or int(weight.shape[1]) != C:
+        raise TypeError(f'weight must be float32 [K, {C}], got {weight.dtype} {tuple(weight.shape)}')
+    K = int(weight.shape[0])
+    if not weight.is_contiguous():
+        raise TypeError(f'weight must be contiguous, got strides {tuple(weight.stride())}')
+    if bias is not None:
+        _require_on_device(bias, 'bias')
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (K,) or not bias.is_contiguous():
+            raise TypeError(f'bias must be contiguous float32 [{K}], got {bias.dtype} {tuple(bias.shape)}')
+    return K
+
+
+def _sh_dtype_code(dtype: torch.dtype, name: str) -> int:
+    codes = {torch.float32: L.NMSA_F32, torch.bfloat16: L.NMSA_BF16, torch.float16: L.NMSA_F16}
+    if dtype not in codes:
+        raise TypeError(f'{name} must be float32, bfloat16 or float16, got {dtype}')
+    return codes[dtype]
+
+
+def scene_head(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], need_pooled: bool = True,
+               out_dtype: Optional[torch.dtype] = None):
+    """`F.linear(F.adaptive_avg_pool2d(x, 1).flatten(1), weight, bias)` in one launch (include/nmsa.h
+    nmsa_scene_head_fwd).  `x` [B, C, H, W] float32 / bfloat16 / float16, dense NCHW on the device; `weight`
+    float32 [K, C], `bias` float32 [K] or None.  Returns (logits, pooled): logits [B, K] in `out_dtype` (x's
+    dtype when None), pooled float32 [B, C], what `scene_head_backward` reads in place of the map.  Without
+    `need_pooled` (inference) none is allocated or written and None is returned for it.  No autograd: that is
+    `model.decoder.SceneHeadFunction`."""
+    code = _mp_check(x, 'x')
+    xc = x.detach()
+    B, C, H, W = (int(n) for n in xc.shape)
+    K = _sh_params(weight, bias, C)
+    out_dtype = xc.dtype if out_dtype is None else out_dtype
+    ocode = _sh_dtype_code(out_dtype, 'out_dtype')
+    logits = torch.empty((B, K), dtype=out_dtype, device=xc.device)
+    pooled = torch.empty((B, C), dtype=torch.float32, device=xc.device) if need_pooled else None
+    L.check(L.lib().nmsa_scene_head_fwd(L.ptr(xc), code, B, C, H, W, L.ptr(weight.detach()),
+                                        L.ptr(None if bias is None else bias.detach()), L.ptr(pooled),
+                                        L.ptr(logits), ocode, K, L.stream_ptr(xc.device)),
+            'nmsa_scene_head_fwd')
+    return logits, pooled
+
+
+def scene_head_backward(g: torch.Tensor, pooled: torch.Tensor, weight: torch.Tensor, x_shape, x_dtype: torch.dtype,
+                        need=(True, True, True)):
+    """(gx, gweight, gbias) of `scene_head` for the upstream gradient `g` [B, K] (float32 / bfloat16 / float16),
+    the forward's `pooled` and `weight`, in one launch (nmsa_scene_head_bwd): gx [B, C, H, W] in `x_dtype`,
+    gweight float32 [K, C], gbias float32 [K]; None where `need` says the gradient is not wanted (nothing is
+    allocated or computed for it).  Every sum runs in a fixed order: the same bits on every call."""
+    _require_on_device(g, 'g')
+    B, C, H, W = (int(n) for n in x_shape)
+    gcode = _sh_dtype_code(g.dtype, 'g')
+    xcode = _sh_dtype_code(x_dtype, 'x_dtype')
+    K = _sh_params(weight, None, C)
+    _require_on_device(pooled, 'pooled')
+    if g.ndim != 2 or tuple(g.shape) != (B, K) or not g.is_contiguous() or min(B, C, H, W) < 1:
+        raise TypeError(f'g must be contiguous [{B}, {K}] for a non-empty map, got {tuple(g.shape)}')
+    if pooled.dtype != torch.float32 or tuple(pooled.shape) != (B, C) or not pooled.is_contiguous():
+        raise TypeError(f'pooled must be contiguous float32 [{B}, {C}], got {pooled.dtype} {tuple(pooled.shape)}')
+    gd = g.detach()
+    dev = gd.device
+    gx = torch.empty((B, C, H, W), dtype=x_dtype, device=dev) if need[0] else None
+    gw = torch.empty((K, C), dtype=torch.float32, device=dev) if need[1] else None
+    gb = torch.empty((K,), dtype=torch.float32, device=dev) if need[2] else None
+    L.check(L.lib().nmsa_scene_head_bwd(L.ptr(gd), gcode, L.ptr(pooled.detach()), L.ptr(weight.detach()), B, C, H, W,
+                                        K, L.ptr(gx), xcode, L.ptr(gw), L.ptr(gb), L.stream_ptr(dev)),
+            'nmsa_scene_head_bwd')
+    return gx, gw, gb
+
+
+def scene_head_route(x: torch.Tensor, n_classes: int = 1) -> int:
+    """The route a call whose map (x forward, gx backward) is `x` [B, C, H, W] takes (`nmsa_scene_head_route`):
+    L.NMSA_SH_ROUTE_UNIT, L.NMSA_SH_ROUTE_VECTOR or L.NMSA_SH_ROUTE_ELEMENT.  Only the shape, the dtype and the
+    address are looked at, nothing is launched."""
+    if x.ndim != 4:
+        raise ValueError('a [B, C, H, W] map')
+    B, C, H, W = (int(n) for n in x.shape)
+    rc = L.lib().nmsa_scene_head_route(L.C.c_void_p(x.data_ptr()), L.float_dtype_code(x), B, C, H, W, int(n_classes))
+    if rc < 0:
+        L.check(rc, 'nmsa_scene_head_route')
+    return rc
+
+
 # ------------------------------------------------------------- orientation MAE on device tables
 def _orientation_table_args(table, name: str, B: int) -> tuple:
     """(keys, angle, valid, n, K, status) of a utils.OrientationTable as the C ABI takes them"""
