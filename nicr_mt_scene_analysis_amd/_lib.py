@@ -283,14 +283,19 @@ def stream_ptr(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+_FLOAT_DTYPE_CODES = {torch.float32: NMSA_F32, torch.bfloat16: NMSA_BF16, torch.float16: NMSA_F16}
+
+
+def float_code_of_dtype(dtype: torch.dtype, name: str = 'tensor') -> int:
+    code = _FLOAT_DTYPE_CODES.get(dtype)
+    if code is None:
+        raise TypeError(f'unsupported floating dtype {dtype} of {name}: float32, bfloat16 or float16')
+    return code
+
+
 def float_dtype_code(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
-        return NMSA_F32
-    if t.dtype == torch.bfloat16:
-        return NMSA_BF16
-    if t.dtype == torch.float16:
-        return NMSA_F16
-    raise TypeError(f'unsupported floating dtype {t.dtype}')
+    code = _FLOAT_DTYPE_CODES.get(t.dtype)          # the lookup itself: this sits on every wrapper's path
+    return float_code_of_dtype(t.dtype) if code is None else code
 
 
 def int_dtype_code(t: torch.Tensor) -> int:

@@ -39,19 +39,14 @@ from .. import ops
 from ..utils import partial_class
 from .activation import get_activation_class
 from .normalization import get_normalization_class
-from .utils import conv1x1, conv3x3
+from .utils import conv1x1, conv3x3, f32_master, fused_map
 
 KNOWN_BLOCKS = ('basicblock', 'bottleneck', 'nonbottleneck1d')
 
-_FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 # elements of a map (B*C*H*W) from which the fused path is taken: measured faster end to end at 8 x 64 x 120 x 160
 # (9.8M) and slower at 8 x 128 x 60 x 80 (2.5M) and below; sizes between the two were not measured
 # and stay on torch
 FUSED_MIN_ELEMENTS = 8 * 2 ** 20
-
-
-def _f32(t: Tensor) -> Tensor:
-    return t if t.dtype == torch.float32 else t.float()
 
 
 class BatchNormTailFunction(torch.autograd.Function):
@@ -104,9 +99,7 @@ class BatchNormTailFunction(torch.autograd.Function):
 
 def _fused_act(norm: nn.Module, act: nn.Module, x: Tensor, identity: Optional[Tensor]) -> Optional[str]:
     """the activation code of the fused HIP path, None when this segment takes the torch composition"""
-    if not (x.is_cuda and x.ndim == 4 and x.dtype in _FUSED_DTYPES and x.numel() > 0 and x.is_contiguous()):
-        return None
-    if x.numel() < FUSED_MIN_ELEMENTS:
+    if not fused_map(x) or x.numel() < FUSED_MIN_ELEMENTS:
         return None
     if identity is not None and not (identity.device == x.device and identity.shape == x.shape
                                      and identity.dtype == x.dtype and identity.is_contiguous()):
@@ -143,9 +136,9 @@ def batch_norm_tail(norm: nn.Module, act: nn.Module, x: Tensor, identity: Option
     if training and x.numel() // x.shape[1] < 2:
         raise ValueError(f'Expected more than 1 value per channel when training, got input size {x.size()}')
     scale = dropout2d_scale(x, dropout.p) if drawing else None
-    rm, rv = _f32(norm.running_mean), _f32(norm.running_var)
-    y = BatchNormTailFunction.apply(x, identity, scale, _f32(norm.weight), _f32(norm.bias), rm, rv, training,
-                                    norm.eps, norm.momentum, code, torch.is_grad_enabled())
+    gamma, beta, rm, rv = f32_master(norm.weight, norm.bias, norm.running_mean, norm.running_var)
+    y = BatchNormTailFunction.apply(x, identity, scale, gamma, beta, rm, rv, training, norm.eps, norm.momentum, code,
+                                    torch.is_grad_enabled())
     if training:
         with torch.no_grad():
             if rm is not norm.running_mean:                 # module.half(): the kernels wrote float32 copies

@@ -36,9 +36,9 @@ from ...types import DecoderInputType
 from ...types import DecoderRawOutputType
 from ...types import EncoderSkipsType
 from ..postprocessing import ScenePostprocessing
+from ..utils import f32_master, fused_map
 from .base import DecoderBase
 
-_FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 # Maps that take the kernels' element route (H W off the 16-byte chunk, or a map off 16 bytes) with more elements
 # per image (C H W) than this run the torch composition.  Measured (docs/measurement_log.md, "Scene decoder"):
 # on that route the one-workgroup-per-image forward takes 27.4 us for a bfloat16 [B, 512, 15, 20] map (153600
@@ -84,7 +84,7 @@ class SceneClassificationDecoder(DecoderBase):
     def takes_hip_path(self, x: Tensor) -> bool:
         """whether the map `x` (the first context feature, or the context module's output) runs the HIP
         kernels (see the module docstring)"""
-        if not (x.is_cuda and x.ndim == 4 and x.dtype in _FUSED_DTYPES and x.numel() > 0 and x.is_contiguous()):
+        if not fused_map(x):
             return False
         head = self._task_head
         if not (x.shape[1] == head.in_features and head.in_features <= L.NMSA_SCENE_HEAD_MAX_CHANNELS
@@ -102,10 +102,7 @@ class SceneClassificationDecoder(DecoderBase):
         if not self.takes_hip_path(x):
             out = self._task_head(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
             return out, None
-        weight, bias = self._task_head.weight, self._task_head.bias
-        if weight.dtype != torch.float32:           # module.half(): the kernel takes f32 weights
-            weight = weight.float()
-            bias = None if bias is None else bias.float()
+        weight, bias = f32_master(self._task_head.weight, self._task_head.bias)
         out_dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
         out = SceneHeadFunction.apply(x, weight, bias, out_dtype, torch.is_grad_enabled())
         return out, None   # there are no side outputs

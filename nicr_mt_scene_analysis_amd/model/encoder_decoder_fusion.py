@@ -36,7 +36,7 @@ from .. import ops
 from ..utils import partial_class
 from .activation import get_activation_class
 from .normalization import get_normalization_class
-from .utils import ConvNormAct
+from .utils import ConvNormAct, f32_master
 
 KNOWN_ENCODER_DECODER_FUSIONS = (
     'add', 'add-rgb', 'add-depth',
@@ -122,9 +122,7 @@ class EncoderDecoderFusionSwin(EncoderDecoderFusion):
         x = self._encoder_features(x_enc)           # NHWC
         if not self._apply_layer_norm:
             return self._fuse_operation(self.layer(torch.permute(x, (0, 3, 1, 2))), x_dec)
-        gamma, beta = self.ln.weight, self.ln.bias
-        if gamma.dtype != torch.float32:            # module.half(): the kernel takes f32 parameters
-            gamma, beta = gamma.float(), beta.float()
+        gamma, beta = f32_master(self.ln.weight, self.ln.bias)
         out_dtype = torch.float32 if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
         identity = isinstance(self.layer, nn.Identity)
         add = None

@@ -32,7 +32,7 @@ from .. import ops
 from ..types import EncoderForwardType
 from ..utils import partial_class
 from .activation import get_activation_class
-from .utils import SqueezeAndExcitation
+from .utils import SqueezeAndExcitation, f32_master, fused_map
 
 KNOWN_ENCODER_FUSIONS = (
     'se-add', 'add',                        # both directions (the same tensor under both keys)
@@ -40,8 +40,6 @@ KNOWN_ENCODER_FUSIONS = (
     'se-add-uni-rgb', 'se-add-uni-depth',   # one direction, SE-weighted
     'none',                                 # no fusion
 )
-
-_FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 def _apply_NCHW_operation(x: Tensor, operation: Callable[[Tensor], Tensor], input_memory_layout: str) -> Tensor:
@@ -54,8 +52,7 @@ def _apply_NCHW_operation(x: Tensor, operation: Callable[[Tensor], Tensor], inpu
 
 def _se_parameters(se: SqueezeAndExcitation) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(W1, b1, W2, b2) of a SqueezeAndExcitation as float32 (a cast copy after module.half())"""
-    params = (se.layers[0].weight, se.layers[0].bias, se.layers[2].weight, se.layers[2].bias)
-    return tuple(p if p.dtype == torch.float32 else p.float() for p in params)
+    return f32_master(se.layers[0].weight, se.layers[0].bias, se.layers[2].weight, se.layers[2].bias)
 
 
 class SEWeightedAddFunction(torch.autograd.Function):
@@ -121,9 +118,8 @@ class EncoderRGBDFusionWeightedAdd(nn.Module):
         """the activation code of the fused HIP path, None when this call takes the torch composition"""
         if self._input_memory_layout != 'nchw':
             return None
-        if not (x_rgb.is_cuda and x_depth.is_cuda and x_rgb.device == x_depth.device and x_rgb.ndim == 4
-                and x_rgb.shape == x_depth.shape and x_rgb.dtype == x_depth.dtype and x_rgb.dtype in _FUSED_DTYPES
-                and x_rgb.numel() > 0 and x_rgb.is_contiguous() and x_depth.is_contiguous()):
+        if not (fused_map(x_rgb) and x_depth.is_cuda and x_rgb.device == x_depth.device
+                and x_rgb.shape == x_depth.shape and x_rgb.dtype == x_depth.dtype and x_depth.is_contiguous()):
             return None
         if torch.is_autocast_enabled('cuda') and \
                 torch.promote_types(x_rgb.dtype, torch.get_autocast_dtype('cuda')) != x_rgb.dtype:

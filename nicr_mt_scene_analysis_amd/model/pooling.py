@@ -18,8 +18,7 @@ from torch import Tensor, nn
 from torch.autograd.function import once_differentiable
 
 from .. import ops
-
-_FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+from .utils import fused_map
 
 
 def _pair(v):
@@ -54,7 +53,7 @@ class MaxPool2d(nn.MaxPool2d):
         if not (_pair(self.kernel_size) == (3, 3) and _pair(stride) == (2, 2) and _pair(self.padding) == (1, 1)
                 and _pair(self.dilation) == (1, 1) and not self.ceil_mode and not self.return_indices):
             return False
-        return bool(x.is_cuda and x.ndim == 4 and x.dtype in _FUSED_DTYPES and x.numel() > 0 and x.is_contiguous())
+        return fused_map(x)
 
     def forward(self, input: Tensor):
         if not self.takes_hip_path(input):

@@ -25,6 +25,7 @@ from torch.nn.functional import interpolate
 
 from .. import ops
 from ..utils import partial_class
+from .utils import f32_master
 
 KNOWN_UPSAMPLING_METHODS = ('nearest', 'bilinear', 'learned-3x3', 'learned-3x3-zeropad')
 
@@ -87,10 +88,7 @@ class Upsampling(nn.Module):
                                align_corners=self._align_corners)
         if x.is_cuda and x.dtype == torch.float32 and torch.is_autocast_enabled('cuda'):
             x = x.to(torch.get_autocast_dtype('cuda'))
-        weight, bias = self.conv.weight, self.conv.bias
-        if weight.dtype != torch.float32:           # module.half(): the kernel takes f32 weights
-            weight = weight.float()
-            bias = None if bias is None else bias.float()
+        weight, bias = f32_master(self.conv.weight, self.conv.bias)
         return LearnedUpsamplingFunction.apply(x, weight, bias, self._zeropad)
 
 

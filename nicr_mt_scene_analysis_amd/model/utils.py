@@ -4,14 +4,31 @@ reference's sub-module names `conv`, `norm`, `act` (the encoder-decoder fusion's
 `SqueezeAndExcitation`, the channel weighting of the encoder RGB-D fusion, with the reference's
 sub-module layout `layers.{0..3}`.  `model.encoder_fusion` reads its parameters for the fused HIP path
 and calls it as it is everywhere else;
-`conv3x3` and `conv1x1`, the bias-free convolutions of the residual blocks (`model.block`)."""
-from typing import Optional, Type
+`conv3x3` and `conv1x1`, the bias-free convolutions of the residual blocks (`model.block`);
+`fused_map` and `f32_master`, what every module with a fused HIP path asks of its input map and does to its
+parameters before it hands them to the kernels."""
+from typing import Optional, Tuple, Type
 
+import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
 from .activation import get_activation_class
 from .normalization import get_normalization_class
+
+FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def fused_map(x: Tensor) -> bool:
+    """whether `x` is a map the fused HIP paths take: on the device, 4-D, float32 / bfloat16 / float16, not empty,
+    dense NCHW.  Each module adds its own terms (channel limits, thresholds, a second tensor)."""
+    return bool(x.is_cuda and x.ndim == 4 and x.dtype in FUSED_DTYPES and x.numel() > 0 and x.is_contiguous())
+
+
+def f32_master(*tensors: Optional[Tensor]) -> Tuple[Optional[Tensor], ...]:
+    """the parameters as the kernels take them, float32: each tensor itself when it is float32 already, a cast
+    copy after `module.half()`, None for None"""
+    return tuple([t if t is None or t.dtype == torch.float32 else t.float() for t in tensors])
 
 
 def conv3x3(in_planes: int, out_planes: int, stride: int = 1, groups: int = 1, dilation: int = 1) -> nn.Conv2d:

@@ -1150,6 +1150,84 @@ def scene_step(logits: torch.Tensor, labels: Optional[torch.Tensor] = None,
     return out
 
 
+# ----------------------------------------------------------------------------- model ops: argument checks
+# What the wrappers from the learned upsampling to the scene head ask of their arguments, said once.  A tensor
+# off the device is a NmsaError, anything else a TypeError (a ValueError where a wrapper says so itself).
+# `dense`: the tensor must be contiguous as it is given (batch-norm tail, max pool, scene head); otherwise the
+# helper hands back a detached, contiguous tensor (a copy only when the caller's is not).  Only addresses, shapes
+# and dtypes of what they hand back are used, so a dense tensor is handed back as it is.  They sit on the eager path
+# of every fused node: nothing is formatted, and `_require_on_device` is not even called, unless a call is refused.
+def _float_map(t: torch.Tensor, name: str = 'x', dense: bool = False) -> int:
+    """the dtype code of a non-empty [B, C, H, W] float32 / bfloat16 / float16 map on the device"""
+    if not t.is_cuda:
+        _require_on_device(t, name)
+    code = L.float_dtype_code(t)                    # TypeError for anything but f32 / bf16 / f16
+    if t.ndim != 4 or t.numel() == 0:
+        raise TypeError(f'{name} must be a non-empty [B, C, H, W] tensor, got shape {tuple(t.shape)}')
+    if dense and not t.is_contiguous():
+        raise TypeError(f'{name} must be dense NCHW, got strides {tuple(t.stride())}')
+    return code
+
+
+def _like(t: Optional[torch.Tensor], shape: tuple, dtype: torch.dtype, device: torch.device, name: str,
+          dense: bool = False) -> Optional[torch.Tensor]:
+    """a further tensor of a call, of exactly this shape, dtype and device; None passes through"""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        _require_on_device(t, name)
+    if t.dtype != dtype or t.shape != shape or t.device != device or (dense and not t.is_contiguous()):
+        raise TypeError(f'{name} must be a {"contiguous " if dense else ""}{dtype} {shape} tensor on {device}, '
+                        f'got {t.dtype} {tuple(t.shape)} on {t.device}')
+    return t if dense else t.detach().contiguous()
+
+
+def _f32(t: Optional[torch.Tensor], shape: tuple, name: str, dense: bool = False) -> Optional[torch.Tensor]:
+    """a float32 parameter or statistics tensor of exactly this shape; None passes through"""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        _require_on_device(t, name)
+    if t.dtype != torch.float32 or t.shape != shape or (dense and not t.is_contiguous()):
+        raise TypeError(f'{name} must be a {"contiguous " if dense else ""}float32 {shape} tensor, '
+                        f'got {t.dtype} {tuple(t.shape)}')
+    return t if dense else t.detach().contiguous()
+
+
+def _out(out: Optional[torch.Tensor], shape: tuple, dtype: torch.dtype, device: torch.device,
+         name: str = 'out') -> torch.Tensor:
+    """the caller's `out=` tensor, or a fresh one"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not out.is_cuda:
+        _require_on_device(out, name)
+    if out.dtype != dtype or out.shape != shape or not out.is_contiguous():
+        raise TypeError(f'{name} must be a contiguous {dtype} {shape} tensor')
+    return out
+
+
+def _choice(value, table: dict, what: str) -> int:
+    if value not in table:
+        raise ValueError(f'{what} must be one of {sorted(table)}, got {value!r}')
+    return table[value]
+
+
+def _ptr_array(tensors):
+    return (L.C.c_void_p * len(tensors))(*(None if t is None else t.data_ptr() for t in tensors))
+
+
+def _int_array(values):
+    return (L.C.c_int * len(values))(*values)
+
+
+def _route(fn_name: str, *args) -> int:
+    """the answer of a route query of the library; NmsaError for a negative one"""
+    rc = getattr(L.lib(), fn_name)(*args)
+    if rc < 0:
+        L.check(rc, fn_name)
+    return rc
+
+
 # ----------------------------------------------------------------------------- learned upsampling
 # partial-sum workspaces of the backward calls (learned upsampling, LayerNorm-transpose), least recently
 # used first out.  One model's set must fit, or every step reallocates: up to five decoders x three
@@ -1160,19 +1238,13 @@ _BWD_WORKSPACES: 'collections.OrderedDict[tuple, torch.Tensor]' = __import__('co
 
 
 def _up_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]):
+    """-> (dtype code of x, weight, bias); a wrong rank or an empty x is a ValueError here"""
     _require_on_device(x, 'x')
     code = L.float_dtype_code(x)                    # TypeError for anything but f32 / bf16 / f16
     if x.ndim != 4 or x.numel() == 0:
         raise ValueError(f'x must be a non-empty [B, C, h, w] tensor, got shape {tuple(x.shape)}')
     C = int(x.shape[1])
-    _require_on_device(weight, 'weight')
-    if weight.dtype != torch.float32 or tuple(weight.shape) != (C, 1, 3, 3):
-        raise TypeError(f'weight must be float32 [{C}, 1, 3, 3], got {weight.dtype} {tuple(weight.shape)}')
-    if bias is not None:
-        _require_on_device(bias, 'bias')
-        if bias.dtype != torch.float32 or tuple(bias.shape) != (C,):
-            raise TypeError(f'bias must be float32 [{C}], got {bias.dtype} {tuple(bias.shape)}')
-    return code
+    return code, _f32(weight, (C, 1, 3, 3), 'weight'), _f32(bias, (C,), 'bias')
 
 
 def _workspace(dev: torch.device, key: tuple, nbytes: int):
@@ -1208,18 +1280,10 @@ def upsample2x_dw3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     [C, 1, 3, 3], `bias` float32 [C] or None.  Returns y [B, C, 2h, 2w] in x's dtype, written into `out`
     when a contiguous tensor of that shape and dtype is given.  No autograd: that is
     `model.upsampling.LearnedUpsamplingFunction`."""
-    code = _up_check(x, weight, bias)
-    xc, w_, b_ = x.detach().contiguous(), weight.detach().contiguous(), None
-    if bias is not None:
-        b_ = bias.detach().contiguous()
+    code, w_, b_ = _up_check(x, weight, bias)
+    xc = x.detach().contiguous()
     B, C, h, w = (int(n) for n in xc.shape)
-    if out is None:
-        y = torch.empty((B, C, 2 * h, 2 * w), dtype=xc.dtype, device=xc.device)
-    else:
-        _require_on_device(out, 'out')
-        if out.dtype != xc.dtype or tuple(out.shape) != (B, C, 2 * h, 2 * w) or not out.is_contiguous():
-            raise TypeError(f'out must be a contiguous {xc.dtype} {(B, C, 2 * h, 2 * w)} tensor')
-        y = out
+    y = _out(out, (B, C, 2 * h, 2 * w), xc.dtype, xc.device)
     L.check(L.lib().nmsa_upsample2x_dw3x3_fwd(
         L.ptr(xc), code, L.ptr(w_), L.ptr(b_), B, C, h, w, int(bool(zeropad)), L.ptr(y),
         L.stream_ptr(xc.device)), 'nmsa_upsample2x_dw3x3_fwd')
@@ -1232,12 +1296,10 @@ def upsample2x_dw3x3_backward(gy: torch.Tensor, x: torch.Tensor, weight: torch.T
     dtype; made contiguous when it is not), None where not needed (nmsa_upsample2x_dw3x3_bwd).  gx has
     x's dtype, gweight [C, 1, 3, 3] and gbias [C] are float32.  Deterministic: a fixed order of
     summation, the same bits on every call."""
-    code = _up_check(x, weight, None)
-    _require_on_device(gy, 'gy')
+    code, w_, _ = _up_check(x, weight, None)
     B, C, h, w = (int(n) for n in x.shape)
-    if gy.dtype != x.dtype or tuple(gy.shape) != (B, C, 2 * h, 2 * w):
-        raise TypeError(f'gy must be {x.dtype} {(B, C, 2 * h, 2 * w)}, got {gy.dtype} {tuple(gy.shape)}')
-    g, xc, w_ = gy.detach().contiguous(), x.detach().contiguous(), weight.detach().contiguous()
+    g = _like(gy, (B, C, 2 * h, 2 * w), x.dtype, x.device, 'gy')
+    xc = x.detach().contiguous()
     dev = xc.device
     gx = torch.empty_like(xc) if need_gx else None
     gw = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=dev) if need_gweight else None
@@ -1257,28 +1319,19 @@ def upsample2x_dw3x3_route(x: torch.Tensor, other: torch.Tensor) -> int:
     if x.ndim != 4:
         raise ValueError(f'x must be [B, C, h, w], got shape {tuple(x.shape)}')
     B, C, h, w = (int(n) for n in x.shape)
-    rc = L.lib().nmsa_upsample2x_dw3x3_route(L.C.c_void_p(x.data_ptr()), L.C.c_void_p(other.data_ptr()),
-                                             L.float_dtype_code(x), B, C, h, w)
-    if rc < 0:
-        L.check(rc, 'nmsa_upsample2x_dw3x3_route')
-    return rc
+    return _route('nmsa_upsample2x_dw3x3_route', x.data_ptr(), other.data_ptr(), L.float_dtype_code(x), B, C, h, w)
 
 
 # ------------------------------------------------------- Swin fusion: LayerNorm + NHWC -> NCHW (+ add)
 def _lnt_check(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor]):
-    """-> (dtype code, B, P, C, spatial shape) of an encoder skip tensor [B, H, W, C] or [B, P, C]"""
+    """-> (dtype code, B, P, C, spatial shape, gamma, beta) of an encoder skip tensor [B, H, W, C] or [B, P, C];
+    a wrong rank or an empty x is a ValueError here"""
     _require_on_device(x, 'x')
     code = L.float_dtype_code(x)                    # TypeError for anything but f32 / bf16 / f16
     if x.ndim not in (3, 4) or x.numel() == 0:
         raise ValueError(f'x must be a non-empty [B, H, W, C] or [B, P, C] tensor, got shape {tuple(x.shape)}')
     B, C, spatial = int(x.shape[0]), int(x.shape[-1]), tuple(int(n) for n in x.shape[1:-1])
-    for t, name in ((gamma, 'gamma'), (beta, 'beta')):
-        if t is None:
-            continue
-        _require_on_device(t, name)
-        if t.dtype != torch.float32 or tuple(t.shape) != (C,):
-            raise TypeError(f'{name} must be float32 [{C}], got {t.dtype} {tuple(t.shape)}')
-    return code, B, int(np.prod(spatial)), C, spatial
+    return code, B, int(np.prod(spatial)), C, spatial, _f32(gamma, (C,), 'gamma'), _f32(beta, (C,), 'beta')
 
 
 def ln_nhwc_to_nchw(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
@@ -1292,25 +1345,14 @@ def ln_nhwc_to_nchw(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, ep
     Written into `out` when a contiguous tensor of that shape and dtype is given.  Returns y, or
     (y, mean, rstd) with `save_stats` (float32 [B*P], what `ln_nhwc_to_nchw_backward` takes).  No
     autograd: that is `model.encoder_decoder_fusion.SwinFusionFunction`."""
-    code, B, P, C, spatial = _lnt_check(x, gamma, beta)
+    code, B, P, C, spatial, g_, b_ = _lnt_check(x, gamma, beta)
     out_dtype = x.dtype if out_dtype is None else out_dtype
     if out_dtype not in (x.dtype, torch.float32):
         raise TypeError(f'out_dtype must be {x.dtype} or torch.float32, got {out_dtype}')
-    xc, g_, b_ = x.detach().contiguous(), gamma.detach().contiguous(), beta.detach().contiguous()
+    xc = x.detach().contiguous()
     shape = (B, C) + spatial
-    a_ = None
-    if add is not None:
-        _require_on_device(add, 'add')
-        if add.dtype != out_dtype or tuple(add.shape) != shape:
-            raise TypeError(f'add must be {out_dtype} {shape}, got {add.dtype} {tuple(add.shape)}')
-        a_ = add.detach().contiguous()
-    if out is None:
-        y = torch.empty(shape, dtype=out_dtype, device=xc.device)
-    else:
-        _require_on_device(out, 'out')
-        if out.dtype != out_dtype or tuple(out.shape) != shape or not out.is_contiguous():
-            raise TypeError(f'out must be a contiguous {out_dtype} {shape} tensor')
-        y = out
+    a_ = _like(add, shape, out_dtype, xc.device, 'add')
+    y = _out(out, shape, out_dtype, xc.device)
     mean = rstd = None
     if save_stats:
         mean = torch.empty((B * P,), dtype=torch.float32, device=xc.device)
@@ -1328,16 +1370,13 @@ def ln_nhwc_to_nchw_backward(gy: torch.Tensor, x: torch.Tensor, gamma: torch.Ten
     or float32; made contiguous when it is not) and the statistics the forward call saved, None where
     not needed (nmsa_ln_nhwc_nchw_bwd).  gx has x's shape and dtype, ggamma and gbeta are float32 [C].
     Deterministic: a fixed order of summation, the same bits on every call."""
-    code, B, P, C, spatial = _lnt_check(x, gamma, None)
-    _require_on_device(gy, 'gy')
-    if gy.dtype not in (x.dtype, torch.float32) or tuple(gy.shape) != (B, C) + spatial:
-        raise TypeError(f'gy must be {x.dtype} or float32 {(B, C) + spatial}, got {gy.dtype} {tuple(gy.shape)}')
-    for t, name in ((mean, 'mean'), (rstd, 'rstd')):
-        _require_on_device(t, name)
-        if t.dtype != torch.float32 or t.numel() != B * P:
-            raise TypeError(f'{name} must be float32 [{B * P}], got {t.dtype} {tuple(t.shape)}')
-    g, xc, g_ = gy.detach().contiguous(), x.detach().contiguous(), gamma.detach().contiguous()
-    m_, r_ = mean.detach().contiguous(), rstd.detach().contiguous()
+    code, B, P, C, spatial, g_, _ = _lnt_check(x, gamma, None)
+    # gy: x's dtype, or float32 (what the forward call wrote under autocast)
+    g = _like(gy, (B, C) + spatial, torch.float32 if gy.dtype == torch.float32 else x.dtype, x.device, 'gy')
+    # the saved statistics: [B * P], and as ever any other shape of that many elements
+    m_ = _f32(mean, mean.shape if mean.numel() == B * P else (B * P,), 'mean')
+    r_ = _f32(rstd, rstd.shape if rstd.numel() == B * P else (B * P,), 'rstd')
+    xc = x.detach().contiguous()
     dev = xc.device
     gx = torch.empty_like(xc) if need_gx else None
     gg = torch.empty((C,), dtype=torch.float32, device=dev) if need_ggamma else None
@@ -1358,11 +1397,8 @@ def ln_nhwc_to_nchw_route(x: torch.Tensor, y: torch.Tensor) -> int:
         raise ValueError(f'x must be [B, H, W, C] or [B, P, C], got shape {tuple(x.shape)}')
     B, C = int(x.shape[0]), int(x.shape[-1])
     P = int(np.prod([int(n) for n in x.shape[1:-1]]))
-    rc = L.lib().nmsa_ln_nhwc_nchw_route(L.C.c_void_p(x.data_ptr()), L.C.c_void_p(y.data_ptr()),
-                                         L.float_dtype_code(x), L.float_dtype_code(y), B, P, C)
-    if rc < 0:
-        L.check(rc, 'nmsa_ln_nhwc_nchw_route')
-    return rc
+    return _route('nmsa_ln_nhwc_nchw_route', x.data_ptr(), y.data_ptr(), L.float_dtype_code(x),
+                  L.float_dtype_code(y), B, P, C)
 
 
 # --------------------------------------------- context module: pyramid pooling, upsample + concat
@@ -1382,10 +1418,6 @@ def _ppm_sizes(sizes) -> Tuple[Tuple[int, int], ...]:
     return tuple(out)
 
 
-def _ppm_ints(values):
-    return (L.C.c_int * len(values))(*values)
-
-
 # sizes as given -> (normalised sizes, ph array, pw array): a model asks for the same few tuples in
 # every step, and building them again is a good part of a call's host time at these map sizes
 _PPM_SIZE_ARGS: dict = {}
@@ -1398,26 +1430,8 @@ def _ppm_size_args(sizes):
         sz = _ppm_sizes(key)
         if len(_PPM_SIZE_ARGS) >= 64:
             _PPM_SIZE_ARGS.clear()
-        hit = _PPM_SIZE_ARGS[key] = (sz, _ppm_ints([s[0] for s in sz]), _ppm_ints([s[1] for s in sz]))
+        hit = _PPM_SIZE_ARGS[key] = (sz, _int_array([s[0] for s in sz]), _int_array([s[1] for s in sz]))
     return hit
-
-
-def _ppm_ptrs(tensors):
-    return (L.C.c_void_p * len(tensors))(*(None if t is None else t.data_ptr() for t in tensors))
-
-
-def _ppm_mode(mode) -> int:
-    if mode not in _PPM_MODES:
-        raise ValueError(f"mode must be 'nearest' or 'bilinear', got {mode!r}")
-    return _PPM_MODES[mode]
-
-
-def _ppm_x_check(x: torch.Tensor, name: str = 'x') -> int:
-    _require_on_device(x, name)
-    code = L.float_dtype_code(x)                    # TypeError for anything but f32 / bf16 / f16
-    if x.ndim != 4 or x.numel() == 0:
-        raise TypeError(f'{name} must be a non-empty [B, C, H, W] tensor, got shape {tuple(x.shape)}')
-    return code
 
 
 def ppm_pool(x: torch.Tensor, sizes) -> Tuple[torch.Tensor, ...]:
@@ -1426,13 +1440,13 @@ def ppm_pool(x: torch.Tensor, sizes) -> Tuple[torch.Tensor, ...]:
     when it is not, channels-last included), `sizes` 1..4 ints or (ph, pw) pairs.  Returns one
     contiguous [B, C, ph, pw] tensor per size in x's dtype: `F.adaptive_avg_pool2d(x, size)` with
     float32 sums.  No autograd: that is `model.context_module.PyramidPoolFunction`."""
-    code = _ppm_x_check(x)
+    code = _float_map(x)
     sz, phs, pws = _ppm_size_args(sizes)
     xc = x.detach().contiguous()
     B, C, H, W = xc.shape
     outs = tuple(torch.empty((B, C, ph, pw), dtype=xc.dtype, device=xc.device) for ph, pw in sz)
     L.check(L.lib().nmsa_ppm_pool_fwd(
-        L.ptr(xc), code, B, C, H, W, len(sz), phs, pws, _ppm_ptrs(outs), L.stream_ptr(xc.device)),
+        L.ptr(xc), code, B, C, H, W, len(sz), phs, pws, _ptr_array(outs), L.stream_ptr(xc.device)),
         'nmsa_ppm_pool_fwd')
     return outs
 
@@ -1447,20 +1461,12 @@ def ppm_pool_backward(gps, x_shape, sizes) -> torch.Tensor:
     given = [g for g in gps if g is not None]
     if len(gps) != len(sz) or not given:
         raise TypeError(f'one gradient (or None) per size and at least one tensor, got {len(gps)} for {len(sz)} sizes')
-    code = _ppm_x_check(given[0], 'gps')
-    gc = []
-    for g, (ph, pw) in zip(gps, sz):
-        if g is None:
-            gc.append(None)
-            continue
-        _require_on_device(g, 'gps')
-        if g.dtype != given[0].dtype or tuple(g.shape) != (B, C, ph, pw):
-            raise TypeError(f'gps must be {given[0].dtype} {(B, C, ph, pw)}, got {g.dtype} {tuple(g.shape)}')
-        gc.append(g.detach().contiguous())
+    code = _float_map(given[0], 'gps')
     dev = given[0].device
+    gc = [_like(g, (B, C, ph, pw), given[0].dtype, dev, 'gps') for g, (ph, pw) in zip(gps, sz)]
     gx = torch.empty((B, C, H, W), dtype=given[0].dtype, device=dev)
     L.check(L.lib().nmsa_ppm_pool_bwd(
-        _ppm_ptrs(gc), code, B, C, H, W, len(sz), phs, pws, L.ptr(gx), L.stream_ptr(dev)), 'nmsa_ppm_pool_bwd')
+        _ptr_array(gc), code, B, C, H, W, len(sz), phs, pws, L.ptr(gx), L.stream_ptr(dev)), 'nmsa_ppm_pool_bwd')
     return gx
 
 
@@ -1472,8 +1478,8 @@ def ppm_upsample_concat(x: torch.Tensor, ys, mode: str = 'bilinear',
     'nearest' or 'bilinear' (align_corners=False).  Returns [B, C + sum Cr_i, H, W], written into `out`
     when a contiguous tensor of that shape and dtype is given.  No autograd: that is
     `model.context_module.UpsampleConcatFunction`."""
-    code = _ppm_x_check(x)
-    m = _ppm_mode(mode)
+    code = _float_map(x)
+    m = _choice(mode, _PPM_MODES, 'mode')
     xc = x.detach().contiguous()
     B, C, H, W = (int(n) for n in xc.shape)
     ys = tuple(ys)
@@ -1486,16 +1492,10 @@ def ppm_upsample_concat(x: torch.Tensor, ys, mode: str = 'bilinear',
             raise TypeError(f'ys must be non-empty {xc.dtype} [{B}, Cr, ph, pw] tensors, got {y.dtype} {tuple(y.shape)}')
         yc.append(y.detach().contiguous())
     shape = (B, C + sum(int(y.shape[1]) for y in yc), H, W)
-    if out is None:
-        o = torch.empty(shape, dtype=xc.dtype, device=xc.device)
-    else:
-        _require_on_device(out, 'out')
-        if out.dtype != xc.dtype or tuple(out.shape) != shape or not out.is_contiguous():
-            raise TypeError(f'out must be a contiguous {xc.dtype} {shape} tensor')
-        o = out
+    o = _out(out, shape, xc.dtype, xc.device)
     L.check(L.lib().nmsa_ppm_upcat_fwd(
-        L.ptr(xc), _ppm_ptrs(yc), code, B, C, H, W, len(yc), _ppm_ints([int(y.shape[1]) for y in yc]),
-        _ppm_ints([int(y.shape[2]) for y in yc]), _ppm_ints([int(y.shape[3]) for y in yc]), m, L.ptr(o),
+        L.ptr(xc), _ptr_array(yc), code, B, C, H, W, len(yc), _int_array([int(y.shape[1]) for y in yc]),
+        _int_array([int(y.shape[2]) for y in yc]), _int_array([int(y.shape[3]) for y in yc]), m, L.ptr(o),
         L.stream_ptr(xc.device)), 'nmsa_ppm_upcat_fwd')
     return o
 
@@ -1507,8 +1507,8 @@ def ppm_upsample_concat_backward(g_out: torch.Tensor, n_channels_x: int, branch_
     `branch_shapes`: the shapes [B, Cr_i, ph_i, pw_i] of the branches; `need`: one bool per branch
     (default all), None is returned for the others.  The gradient of x is the view
     `g_out[:, :n_channels_x]`: no kernel.  Deterministic: a gather in a fixed order."""
-    code = _ppm_x_check(g_out, 'g_out')
-    m = _ppm_mode(mode)
+    code = _float_map(g_out, 'g_out')
+    m = _choice(mode, _PPM_MODES, 'mode')
     shapes = [tuple(int(n) for n in s) for s in branch_shapes]
     if not 1 <= len(shapes) <= L.NMSA_PPM_MAX_BINS:
         raise ValueError(f'1..{L.NMSA_PPM_MAX_BINS} branches per call, got {len(shapes)}')
@@ -1521,8 +1521,8 @@ def ppm_upsample_concat_backward(g_out: torch.Tensor, n_channels_x: int, branch_
     g = g_out.detach().contiguous()
     gys = tuple(torch.empty(s, dtype=g.dtype, device=g.device) if n else None for s, n in zip(shapes, need))
     L.check(L.lib().nmsa_ppm_upcat_bwd(
-        L.ptr(g), code, B, C, H, W, len(shapes), _ppm_ints([s[1] for s in shapes]),
-        _ppm_ints([s[2] for s in shapes]), _ppm_ints([s[3] for s in shapes]), m, _ppm_ptrs(gys),
+        L.ptr(g), code, B, C, H, W, len(shapes), _int_array([s[1] for s in shapes]),
+        _int_array([s[2] for s in shapes]), _int_array([s[3] for s in shapes]), m, _ptr_array(gys),
         L.stream_ptr(g.device)), 'nmsa_ppm_upcat_bwd')
     return gys
 
@@ -1532,21 +1532,12 @@ def ppm_route(hw: Tuple[int, int], sizes) -> int:
     these pool sizes (`nmsa_ppm_route`): L.NMSA_PPM_ROUTE_LDS or L.NMSA_PPM_ROUTE_GLOBAL.  Host only,
     nothing is launched."""
     sz, phs, pws = _ppm_size_args(sizes)
-    rc = L.lib().nmsa_ppm_route(int(hw[0]), int(hw[1]), len(sz), phs, pws)
-    if rc < 0:
-        L.check(rc, 'nmsa_ppm_route')
-    return rc
+    return _route('nmsa_ppm_route', int(hw[0]), int(hw[1]), len(sz), phs, pws)
 
 
 # ------------------------------------------------ MLP decoders: all branches into the concatenation
 _MLPDEC_MODES = {'nearest': L.NMSA_MLPDEC_NEAREST, 'bilinear': L.NMSA_MLPDEC_BILINEAR}
 _MLPDEC_MAX_SHIFT = 4
-
-
-def _mlpdec_mode(mode) -> int:
-    if mode not in _MLPDEC_MODES:
-        raise ValueError(f"mode must be 'nearest' or 'bilinear', got {mode!r}")
-    return _MLPDEC_MODES[mode]
 
 
 def _mlpdec_shifts(shapes, size=None) -> Tuple[int, int, Tuple[int, ...]]:
@@ -1581,11 +1572,11 @@ def mlpdec_upsample_concat(ys, mode: str = 'bilinear', size=None) -> torch.Tenso
     'nearest' or 'bilinear' (align_corners=False); a branch that is already H x W is copied.  Returns
     [B, sum c_i, H, W].  No autograd: that is `model.decoder.MlpUpsampleConcatFunction`."""
     ys = tuple(ys)
-    m = _mlpdec_mode(mode)
+    m = _choice(mode, _MLPDEC_MODES, 'mode')
     for y in ys:
         _require_on_device(y, 'ys')
     H, W, shifts = _mlpdec_shifts([tuple(y.shape) for y in ys], size)
-    code = _ppm_x_check(ys[0], 'ys')
+    code = _float_map(ys[0], 'ys')
     B = int(ys[0].shape[0])
     yc = []
     for y in ys:
@@ -1596,7 +1587,7 @@ def mlpdec_upsample_concat(ys, mode: str = 'bilinear', size=None) -> torch.Tenso
     cs = [int(y.shape[1]) for y in yc]
     out = torch.empty((B, sum(cs), H, W), dtype=yc[0].dtype, device=yc[0].device)
     L.check(L.lib().nmsa_mlpdec_upcat_fwd(
-        _ppm_ptrs(yc), code, B, H, W, len(yc), _ppm_ints(cs), _ppm_ints(shifts), m, L.ptr(out),
+        _ptr_array(yc), code, B, H, W, len(yc), _int_array(cs), _int_array(shifts), m, L.ptr(out),
         L.stream_ptr(out.device)), 'nmsa_mlpdec_upcat_fwd')
     return out
 
@@ -1608,8 +1599,8 @@ def mlpdec_upsample_concat_backward(g_out: torch.Tensor, branch_shapes, mode: st
     `branch_shapes`: the shapes [B, c_i, h_i, w_i]; `need`: one bool per branch (default all), None is
     returned for the others.  The gradient of a branch that is already H x W is the view
     `g_out[:, off_i:off_i + c_i]`: no kernel.  Deterministic: a gather in a fixed order."""
-    code = _ppm_x_check(g_out, 'g_out')
-    m = _mlpdec_mode(mode)
+    code = _float_map(g_out, 'g_out')
+    m = _choice(mode, _MLPDEC_MODES, 'mode')
     shapes = [tuple(int(n) for n in s) for s in branch_shapes]
     H, W, shifts = _mlpdec_shifts(shapes, (g_out.shape[2], g_out.shape[3]) if g_out.ndim == 4 else None)
     need = [True] * len(shapes) if need is None else [bool(n) for n in need]
@@ -1630,8 +1621,8 @@ def mlpdec_upsample_concat_backward(g_out: torch.Tensor, branch_shapes, mode: st
     asked = [t if t is not None and sh else None for t, sh in zip(gys, shifts)]
     if any(t is not None for t in asked):
         L.check(L.lib().nmsa_mlpdec_upcat_bwd(
-            L.ptr(g), code, B, H, W, len(shapes), _ppm_ints([s[1] for s in shapes]), _ppm_ints(shifts), m,
-            _ppm_ptrs(asked), L.stream_ptr(g.device)), 'nmsa_mlpdec_upcat_bwd')
+            L.ptr(g), code, B, H, W, len(shapes), _int_array([s[1] for s in shapes]), _int_array(shifts), m,
+            _ptr_array(asked), L.stream_ptr(g.device)), 'nmsa_mlpdec_upcat_bwd')
     return tuple(gys)
 
 
@@ -1642,57 +1633,25 @@ def mlpdec_route(ys, out: torch.Tensor) -> int:
     launched; the backward has one route."""
     ys = tuple(ys)
     H, W, shifts = _mlpdec_shifts([tuple(y.shape) for y in ys], (out.shape[2], out.shape[3]))
-    rc = L.lib().nmsa_mlpdec_route(_ppm_ptrs(ys), L.ptr(out), L.float_dtype_code(out), H, W, len(ys),
-                                   _ppm_ints(shifts))
-    if rc < 0:
-        L.check(rc, 'nmsa_mlpdec_route')
-    return rc
+    return _route('nmsa_mlpdec_route', _ptr_array(ys), L.ptr(out), L.float_dtype_code(out), H, W, len(ys),
+                  _int_array(shifts))
 
 
 # ------------------------------------------------------- encoder RGB-D fusion: SE-weighted add
 _SEFUSE_ACTS = {'relu': L.NMSA_SEFUSE_ACT_RELU, 'silu': L.NMSA_SEFUSE_ACT_SILU}
 
 
-def _sefuse_act(act) -> int:
-    if act not in _SEFUSE_ACTS:
-        raise ValueError(f"act must be 'relu' or 'silu', got {act!r}")
-    return _SEFUSE_ACTS[act]
-
-
 def _sefuse_maps(first: torch.Tensor, others, names) -> Tuple[int, Tuple[int, int, int, int], list]:
     """dtype code, (B, C, H, W) and the detached, contiguous maps of a call: `first` sets device, dtype
     and shape, every tensor of `others` (None allowed) must match it"""
-    code = _ppm_x_check(first, names[0])
+    code = _float_map(first, names[0])
     shape = tuple(int(n) for n in first.shape)
     if shape[1] < 16:
         raise ValueError(f'the SE weighting needs at least 16 channels, got {shape[1]}')
     maps = [first.detach().contiguous()]
     for t, name in zip(others, names[1:]):
-        if t is None:
-            maps.append(None)
-            continue
-        _require_on_device(t, name)
-        if t.dtype != first.dtype or tuple(t.shape) != shape or t.device != first.device:
-            raise TypeError(f'{name} must be {first.dtype} {shape} on {first.device}, got {t.dtype} '
-                            f'{tuple(t.shape)} on {t.device}')
-        maps.append(t.detach().contiguous())
+        maps.append(_like(t, shape, first.dtype, first.device, name))
     return code, shape, maps
-
-
-def _sefuse_vec(t: torch.Tensor, shape, name: str) -> torch.Tensor:
-    _require_on_device(t, name)
-    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
-        raise TypeError(f'{name} must be float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
-    return t.detach().contiguous()
-
-
-def _sefuse_out(out, shape, dtype, device, name: str) -> torch.Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    _require_on_device(out, name)
-    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
-        raise TypeError(f'{name} must be a contiguous {dtype} {tuple(shape)} tensor')
-    return out
 
 
 def _sefuse_params(params, C: int, device, n_each: int):
@@ -1715,7 +1674,7 @@ def _sefuse_params(params, C: int, device, n_each: int):
             t = t.detach().contiguous()
             keep.append(t)
             flat.append(t)
-    return keep, _ppm_ptrs(flat)
+    return keep, _ptr_array(flat)
 
 
 def sefuse_squeeze(x_rgb: torch.Tensor, x_depth: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1723,7 +1682,7 @@ def sefuse_squeeze(x_rgb: torch.Tensor, x_depth: torch.Tensor, out: Optional[tor
     one dtype (float32 / bfloat16 / float16) on the device, in one launch (include/nmsa.h
     nmsa_sefuse_squeeze): float32 sums in a fixed order, no atomics."""
     code, (B, C, H, W), (xr, xd) = _sefuse_maps(x_rgb, (x_depth,), ('x_rgb', 'x_depth'))
-    s = _sefuse_out(out, (2, B, C), torch.float32, xr.device, 'out')
+    s = _out(out, (2, B, C), torch.float32, xr.device)
     L.check(L.lib().nmsa_sefuse_squeeze(L.ptr(xr), L.ptr(xd), code, B, C, H, W, L.ptr(s), L.stream_ptr(xr.device)),
             'nmsa_sefuse_squeeze')
     return s
@@ -1734,7 +1693,7 @@ def sefuse_excite(s: torch.Tensor, params_rgb, params_depth, act: str = 'relu', 
     in one launch (nmsa_sefuse_excite).  `params_*`: (W1 [C//16, C], b1, W2 [C, C//16], b2) float32 on the
     device (the 1x1 convolution weights as they are); `act` 'relu' or 'silu'.  With `save_z1` returns
     (w, z1), z1 float32 [2, B, C//16] the hidden pre-activation `sefuse_excite_backward` takes."""
-    a = _sefuse_act(act)
+    a = _choice(act, _SEFUSE_ACTS, 'act')
     _require_on_device(s, 's')
     if s.ndim != 3 or s.shape[0] != 2 or s.dtype != torch.float32 or s.numel() == 0:
         raise TypeError(f's must be a non-empty float32 [2, B, C] tensor, got {s.dtype} {tuple(s.shape)}')
@@ -1758,8 +1717,8 @@ def sefuse_scale_add(x_rgb: torch.Tensor, x_depth: torch.Tensor, w: torch.Tensor
     (nmsa_sefuse_scale_add): float32 arithmetic, one rounding to the maps' dtype.  `w` float32
     [2, B, C]; written into `out` when a contiguous tensor of the maps' shape and dtype is given."""
     code, (B, C, H, W), (xr, xd) = _sefuse_maps(x_rgb, (x_depth,), ('x_rgb', 'x_depth'))
-    wc = _sefuse_vec(w, (2, B, C), 'w')
-    y = _sefuse_out(out, (B, C, H, W), xr.dtype, xr.device, 'out')
+    wc = _f32(w, (2, B, C), 'w')
+    y = _out(out, (B, C, H, W), xr.dtype, xr.device)
     L.check(L.lib().nmsa_sefuse_scale_add(L.ptr(xr), L.ptr(xd), code, L.ptr(wc), B, C, H, W, L.ptr(y),
                                           L.stream_ptr(xr.device)), 'nmsa_sefuse_scale_add')
     return y
@@ -1772,7 +1731,7 @@ def sefuse_weight_grad(gy: torch.Tensor, x_rgb: Optional[torch.Tensor], x_depth:
     read and its half of gw is zero (left as it is in a given `out`)."""
     code, (B, C, H, W), (g, xr, xd) = _sefuse_maps(gy, (x_rgb, x_depth), ('gy', 'x_rgb', 'x_depth'))
     if out is not None:
-        gw = _sefuse_out(out, (2, B, C), torch.float32, g.device, 'out')
+        gw = _out(out, (2, B, C), torch.float32, g.device)
     elif xr is None or xd is None:
         gw = torch.zeros((2, B, C), dtype=torch.float32, device=g.device)
     else:
@@ -1788,7 +1747,7 @@ def sefuse_excite_backward(gw: torch.Tensor, w: torch.Tensor, z1: torch.Tensor, 
     weight gradient `gw` in one launch (nmsa_sefuse_excite_bwd): gz2 = gw w (1 - w), gz1 = (W2^T gz2)
     act'(z1), gs = W1^T gz1, h = act(z1).  `weights_*`: (W1, W2) of the modality, or None: that
     modality is not wanted and its halves are zero."""
-    a = _sefuse_act(act)
+    a = _choice(act, _SEFUSE_ACTS, 'act')
     _require_on_device(gw, 'gw')
     if gw.ndim != 3 or gw.shape[0] != 2 or gw.numel() == 0:
         raise TypeError(f'gw must be a non-empty float32 [2, B, C] tensor, got {tuple(gw.shape)}')
@@ -1796,9 +1755,9 @@ def sefuse_excite_backward(gw: torch.Tensor, w: torch.Tensor, z1: torch.Tensor, 
     if C < 16:
         raise ValueError(f'the SE weighting needs at least 16 channels, got {C}')
     R = C // 16
-    g = _sefuse_vec(gw, (2, B, C), 'gw')
-    wc = _sefuse_vec(w, (2, B, C), 'w')
-    z = _sefuse_vec(z1, (2, B, R), 'z1')
+    g = _f32(gw, (2, B, C), 'gw')
+    wc = _f32(w, (2, B, C), 'w')
+    z = _f32(z1, (2, B, R), 'z1')
     keep, ptrs = _sefuse_params((weights_rgb, weights_depth), C, g.device, 2)
     make = torch.empty if len(keep) == 4 else torch.zeros
     gz2, gs = (make((2, B, C), dtype=torch.float32, device=g.device) for _ in range(2))
@@ -1814,10 +1773,10 @@ def sefuse_apply_backward(gy: torch.Tensor, w: torch.Tensor, gs: torch.Tensor, n
     """(gx_rgb, gx_depth), gx_m = gy * w[m] + gs[m] / (H * W), in gy's dtype in one launch
     (nmsa_sefuse_apply_bwd); None for a modality that is not needed."""
     code, (B, C, H, W), (g,) = _sefuse_maps(gy, (), ('gy',))
-    wc = _sefuse_vec(w, (2, B, C), 'w')
-    gsc = _sefuse_vec(gs, (2, B, C), 'gs')
-    gxr = _sefuse_out(out_rgb, (B, C, H, W), g.dtype, g.device, 'out_rgb') if need_rgb else None
-    gxd = _sefuse_out(out_depth, (B, C, H, W), g.dtype, g.device, 'out_depth') if need_depth else None
+    wc = _f32(w, (2, B, C), 'w')
+    gsc = _f32(gs, (2, B, C), 'gs')
+    gxr = _out(out_rgb, (B, C, H, W), g.dtype, g.device, 'out_rgb') if need_rgb else None
+    gxd = _out(out_depth, (B, C, H, W), g.dtype, g.device, 'out_depth') if need_depth else None
     if need_rgb or need_depth:
         L.check(L.lib().nmsa_sefuse_apply_bwd(L.ptr(g), code, L.ptr(wc), L.ptr(gsc), B, C, H, W, L.ptr(gxr),
                                               L.ptr(gxd), L.stream_ptr(g.device)), 'nmsa_sefuse_apply_bwd')
@@ -1832,49 +1791,24 @@ def sefuse_route(*tensors: torch.Tensor) -> int:
     L.NMSA_SEFUSE_WAVE_PLANE_MAX elements, one workgroup above).  Host only, nothing is launched."""
     if not 1 <= len(tensors) <= 3 or any(t.ndim != 4 for t in tensors):
         raise ValueError('1..3 [B, C, H, W] tensors')
-    ptrs = [L.C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (3 - len(tensors))
-    rc = L.lib().nmsa_sefuse_route(*ptrs, L.float_dtype_code(tensors[0]), int(tensors[0].shape[2]),
-                                   int(tensors[0].shape[3]))
-    if rc < 0:
-        L.check(rc, 'nmsa_sefuse_route')
-    return rc
+    ptrs = [t.data_ptr() for t in tensors] + [None] * (3 - len(tensors))
+    return _route('nmsa_sefuse_route', *ptrs, L.float_dtype_code(tensors[0]), int(tensors[0].shape[2]),
+                  int(tensors[0].shape[3]))
 
 
 # ------------------------------------------------------- residual blocks: the fused batch-norm tail
 _BNTAIL_ACTS = {'relu': L.NMSA_BNTAIL_ACT_RELU, 'silu': L.NMSA_BNTAIL_ACT_SILU}
 
 
-def _bntail_act(act) -> int:
-    if act not in _BNTAIL_ACTS:
-        raise ValueError(f"act must be 'relu' or 'silu', got {act!r}")
-    return _BNTAIL_ACTS[act]
-
-
 def _bntail_maps(first: torch.Tensor, others, names):
     """dtype code, (B, C, H, W) and the detached maps of a call: `first` sets device, dtype and shape, every
     tensor of `others` (None allowed) must match it; all must be dense NCHW"""
-    code = _ppm_x_check(first, names[0])
+    code = _float_map(first, names[0], dense=True)
     shape = tuple(int(n) for n in first.shape)
-    maps = []
-    for t, name in zip((first,) + tuple(others), names):
-        if t is None:
-            maps.append(None)
-            continue
-        _require_on_device(t, name)
-        if t.dtype != first.dtype or tuple(t.shape) != shape or t.device != first.device or not t.is_contiguous():
-            raise TypeError(f'{name} must be a contiguous {first.dtype} {shape} tensor on {first.device}, got '
-                            f'{t.dtype} {tuple(t.shape)} on {t.device}')
-        maps.append(t.detach())
+    maps = [first]
+    for t, name in zip(others, names[1:]):
+        maps.append(_like(t, shape, first.dtype, first.device, name, dense=True))
     return code, shape, maps
-
-
-def _bntail_vec(t: Optional[torch.Tensor], C: int, name: str) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    _require_on_device(t, name)
-    if t.dtype != torch.float32 or tuple(t.shape) != (C,) or not t.is_contiguous():
-        raise TypeError(f'{name} must be a contiguous float32 [{C}] tensor, got {t.dtype} {tuple(t.shape)}')
-    return t.detach()
 
 
 def _bntail_scale(scale: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
@@ -1924,15 +1858,16 @@ def bntail_apply(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, runni
     `running_var` (float32 [C]) are UPDATED in place with `momentum`.  `part` None: eval, they are read.
     `identity` (x's shape and dtype) and `scale` ([B, C] of x's dtype, the Dropout2d scale) are optional.
     With `save` returns (y, mean, invstd), the float32 [C] statistics `bntail_backward_*` take."""
-    a = _bntail_act(act)
+    a = _choice(act, _BNTAIL_ACTS, 'act')
     code, shape, (xc, idc) = _bntail_maps(x, (identity,), ('x', 'identity'))
     B, C, H, W = shape
     if part is not None and B * H * W < 2:
         raise ValueError(f'Expected more than 1 value per channel when training, got input size {list(shape)}')
     sc = _bntail_scale(scale, xc)
-    g, b = _bntail_vec(gamma, C, 'gamma'), _bntail_vec(beta, C, 'beta')
-    rm, rv = _bntail_vec(running_mean, C, 'running_mean'), _bntail_vec(running_var, C, 'running_var')
-    y = _sefuse_out(out, shape, xc.dtype, xc.device, 'out')
+    g, b = _f32(gamma, (C,), 'gamma', dense=True), _f32(beta, (C,), 'beta', dense=True)
+    rm = _f32(running_mean, (C,), 'running_mean', dense=True)
+    rv = _f32(running_var, (C,), 'running_var', dense=True)
+    y = _out(out, shape, xc.dtype, xc.device)
     mean = torch.empty((C,), dtype=torch.float32, device=xc.device) if save else None
     invstd = torch.empty((C,), dtype=torch.float32, device=xc.device) if save else None
     nbytes = 0
@@ -1946,12 +1881,13 @@ def bntail_apply(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, runni
 
 
 def _bntail_bwd_args(gy, x, aux, scale, gamma, beta, mean, invstd, act):
-    a = _bntail_act(act)
+    a = _choice(act, _BNTAIL_ACTS, 'act')
     code, shape, (g, xc, ac) = _bntail_maps(gy, (x, aux), ('gy', 'x', 'aux'))
     if xc is None or (a == L.NMSA_BNTAIL_ACT_RELU and ac is None):
         raise TypeError("x is needed, and under 'relu' aux (the saved output y)")
     C = shape[1]
-    vecs = [_bntail_vec(t, C, n) for t, n in ((gamma, 'gamma'), (beta, 'beta'), (mean, 'mean'), (invstd, 'invstd'))]
+    vecs = [_f32(t, (C,), n, dense=True)
+            for t, n in ((gamma, 'gamma'), (beta, 'beta'), (mean, 'mean'), (invstd, 'invstd'))]
     head = (L.ptr(g), L.ptr(xc), L.ptr(ac), L.ptr(_bntail_scale(scale, g)), code, *shape,
             *(L.ptr(v) for v in vecs), a)
     return head, shape, g, (xc, ac, vecs)
@@ -1989,8 +1925,8 @@ def bntail_backward_apply(gy: torch.Tensor, x: torch.Tensor, aux: Optional[torch
     nbytes = 0
     if part is not None:
         part, nbytes = _bntail_part(part, shape, g.device)
-    gx = _sefuse_out(out_x, shape, g.dtype, g.device, 'out_x') if need_x else None
-    gid = _sefuse_out(out_identity, shape, g.dtype, g.device, 'out_identity') if need_identity else None
+    gx = _out(out_x, shape, g.dtype, g.device, 'out_x') if need_x else None
+    gid = _out(out_identity, shape, g.dtype, g.device, 'out_identity') if need_identity else None
     dgamma = torch.empty((shape[1],), dtype=torch.float32, device=g.device) if need_params else None
     dbeta = torch.empty((shape[1],), dtype=torch.float32, device=g.device) if need_params else None
     if need_x or need_identity or need_params:
@@ -2006,12 +1942,10 @@ def bntail_route(*tensors: torch.Tensor) -> Tuple[int, int]:
     (ceil(H*W / L.NMSA_BNTAIL_SEGMENT)).  Host only, nothing is launched."""
     if not 1 <= len(tensors) <= 5 or any(t.ndim != 4 for t in tensors):
         raise ValueError('1..5 [B, C, H, W] tensors')
-    ptrs = [L.C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (5 - len(tensors))
+    ptrs = [t.data_ptr() for t in tensors] + [None] * (5 - len(tensors))
     seg = L.C.c_int(0)
-    rc = L.lib().nmsa_bntail_route(*ptrs, L.float_dtype_code(tensors[0]), int(tensors[0].shape[2]),
-                                   int(tensors[0].shape[3]), L.C.byref(seg))
-    if rc < 0:
-        L.check(rc, 'nmsa_bntail_route')
+    rc = _route('nmsa_bntail_route', *ptrs, L.float_dtype_code(tensors[0]), int(tensors[0].shape[2]),
+                int(tensors[0].shape[3]), L.C.byref(seg))
     return rc, seg.value
 
 
@@ -2021,13 +1955,6 @@ def maxpool3x3s2_out_shape(shape) -> Tuple[int, int, int, int]:
     return B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1
 
 
-def _mp_check(x: torch.Tensor, name: str) -> int:
-    code = _ppm_x_check(x, name)
-    if not x.is_contiguous():
-        raise TypeError(f'{name} must be dense NCHW, got strides {tuple(x.stride())}')
-    return code
-
-
 def maxpool3x3s2(x: torch.Tensor, need_code: bool = True, out: Optional[torch.Tensor] = None):
     """`F.max_pool2d(x, 3, 2, 1)` in one launch (include/nmsa.h nmsa_maxpool3x3s2_fwd).  `x` [B, C, H, W] float32
     / bfloat16 / float16, dense NCHW on the device.  Returns (y, code): y [B, C, Ho, Wo] in x's dtype carries the
@@ -2035,11 +1962,11 @@ def maxpool3x3s2(x: torch.Tensor, need_code: bool = True, out: Optional[torch.Te
     window position 0..8 of the selected pixel, what `maxpool3x3s2_backward` reads in place of ATen's int64 index.
     Without `need_code` (inference) none is allocated or written and None is returned for it.  No autograd:
     that is `model.pooling.MaxPool3x3S2Function`."""
-    code = _mp_check(x, 'x')
+    code = _float_map(x, 'x', dense=True)
     xc = x.detach()
     B, C, H, W = (int(n) for n in xc.shape)
     oshape = maxpool3x3s2_out_shape(xc.shape)
-    y = _sefuse_out(out, oshape, xc.dtype, xc.device, 'out')
+    y = _out(out, oshape, xc.dtype, xc.device)
     k = torch.empty(oshape, dtype=torch.uint8, device=xc.device) if need_code else None
     L.check(L.lib().nmsa_maxpool3x3s2_fwd(L.ptr(xc), code, B, C, H, W, L.ptr(y), L.ptr(k), L.stream_ptr(xc.device)),
             'nmsa_maxpool3x3s2_fwd')
@@ -2051,18 +1978,16 @@ def maxpool3x3s2_backward(gy: torch.Tensor, code: torch.Tensor, input_hw: Tuple[
     """gx [B, C, H, W] of `maxpool3x3s2` for the upstream gradient `gy` [B, C, Ho, Wo] and the forward's `code`
     in one launch (nmsa_maxpool3x3s2_bwd): a gather, every element written, float32 sums in a fixed order
     (oy, then ox, ascending) rounded once: the same bits on every call."""
-    dcode = _mp_check(gy, 'gy')
+    dcode = _float_map(gy, 'gy', dense=True)
     H, W = (int(n) for n in input_hw)
     B, C = int(gy.shape[0]), int(gy.shape[1])
     oshape = maxpool3x3s2_out_shape((B, C, H, W))
-    _require_on_device(code, 'code')
-    if tuple(gy.shape) != oshape or tuple(code.shape) != oshape or code.dtype != torch.uint8 \
-            or not code.is_contiguous() or code.device != gy.device:
-        raise TypeError(f'gy and code (uint8, contiguous) must be {oshape} for an input of {H}x{W}, got '
-                        f'{tuple(gy.shape)} and {code.dtype} {tuple(code.shape)}')
+    k = _like(code, oshape, torch.uint8, gy.device, 'code', dense=True)
+    if tuple(gy.shape) != oshape:
+        raise TypeError(f'gy must be {oshape} for an input of {H}x{W}, got {tuple(gy.shape)}')
     g = gy.detach()
-    gx = _sefuse_out(out, (B, C, H, W), g.dtype, g.device, 'out')
-    L.check(L.lib().nmsa_maxpool3x3s2_bwd(L.ptr(g), L.ptr(code), dcode, B, C, H, W, L.ptr(gx), L.stream_ptr(g.device)),
+    gx = _out(out, (B, C, H, W), g.dtype, g.device)
+    L.check(L.lib().nmsa_maxpool3x3s2_bwd(L.ptr(g), L.ptr(k), dcode, B, C, H, W, L.ptr(gx), L.stream_ptr(g.device)),
             'nmsa_maxpool3x3s2_bwd')
     return gx
 
@@ -2077,35 +2002,17 @@ def maxpool3x3s2_route(x: torch.Tensor, *others: torch.Tensor) -> int:
     B, C, H, W = (int(n) for n in x.shape)
     route = L.NMSA_MP_ROUTE_VECTOR
     for t in others:
-        rc = L.lib().nmsa_maxpool3x3s2_route(L.C.c_void_p(x.data_ptr()), L.C.c_void_p(t.data_ptr()),
-                                             L.float_dtype_code(x), B, C, H, W)
-        if rc < 0:
-            L.check(rc, 'nmsa_maxpool3x3s2_route')
-        if rc != L.NMSA_MP_ROUTE_VECTOR:
+        if _route('nmsa_maxpool3x3s2_route', x.data_ptr(), t.data_ptr(), L.float_dtype_code(x), B, C, H,
+                  W) != L.NMSA_MP_ROUTE_VECTOR:
             route = L.NMSA_MP_ROUTE_PIXEL
     return route
 
 
 # ------------------------------------------------------------- the scene classification decoder
 def _sh_params(weight: torch.Tensor, bias: Optional[torch.Tensor], C: int):
-    _require_on_device(weight, 'weight')
-    if weight.ndim != 2 or weight.dtype != torch.float32 or int(weight.shape[1]) != C:
-        raise TypeError(f'weight must be float32 [K, {C}], got {weight.dtype} {tuple(weight.shape)}')
-    K = int(weight.shape[0])
-    if not weight.is_contiguous():
-        raise TypeError(f'weight must be contiguous, got strides {tuple(weight.stride())}')
-    if bias is not None:
-        _require_on_device(bias, 'bias')
-        if bias.dtype != torch.float32 or tuple(bias.shape) != (K,) or not bias.is_contiguous():
-            raise TypeError(f'bias must be contiguous float32 [{K}], got {bias.dtype} {tuple(bias.shape)}')
-    return K
-
-
-def _sh_dtype_code(dtype: torch.dtype, name: str) -> int:
-    codes = {torch.float32: L.NMSA_F32, torch.bfloat16: L.NMSA_BF16, torch.float16: L.NMSA_F16}
-    if dtype not in codes:
-        raise TypeError(f'{name} must be float32, bfloat16 or float16, got {dtype}')
-    return codes[dtype]
+    """-> (K, weight, bias) of a linear layer over C channels: float32 [K, C] and [K] (or None), dense"""
+    K = int(weight.shape[0]) if weight.ndim == 2 else -1            # -1: no [K, C] at all, refused below
+    return K, _f32(weight, (K, C), 'weight', dense=True), _f32(bias, (K,), 'bias', dense=True)
 
 
 def scene_head(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], need_pooled: bool = True,
@@ -2116,16 +2023,15 @@ def scene_head(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     dtype when None), pooled float32 [B, C], what `scene_head_backward` reads in place of the map.  Without
     `need_pooled` (inference) none is allocated or written and None is returned for it.  No autograd: that is
     `model.decoder.SceneHeadFunction`."""
-    code = _mp_check(x, 'x')
+    code = _float_map(x, 'x', dense=True)
     xc = x.detach()
     B, C, H, W = (int(n) for n in xc.shape)
-    K = _sh_params(weight, bias, C)
+    K, w_, b_ = _sh_params(weight, bias, C)
     out_dtype = xc.dtype if out_dtype is None else out_dtype
-    ocode = _sh_dtype_code(out_dtype, 'out_dtype')
+    ocode = L.float_code_of_dtype(out_dtype, 'out_dtype')
     logits = torch.empty((B, K), dtype=out_dtype, device=xc.device)
     pooled = torch.empty((B, C), dtype=torch.float32, device=xc.device) if need_pooled else None
-    L.check(L.lib().nmsa_scene_head_fwd(L.ptr(xc), code, B, C, H, W, L.ptr(weight.detach()),
-                                        L.ptr(None if bias is None else bias.detach()), L.ptr(pooled),
+    L.check(L.lib().nmsa_scene_head_fwd(L.ptr(xc), code, B, C, H, W, L.ptr(w_), L.ptr(b_), L.ptr(pooled),
                                         L.ptr(logits), ocode, K, L.stream_ptr(xc.device)),
             'nmsa_scene_head_fwd')
     return logits, pooled
@@ -2139,22 +2045,19 @@ def scene_head_backward(g: torch.Tensor, pooled: torch.Tensor, weight: torch.Ten
     allocated or computed for it).  Every sum runs in a fixed order: the same bits on every call."""
     _require_on_device(g, 'g')
     B, C, H, W = (int(n) for n in x_shape)
-    gcode = _sh_dtype_code(g.dtype, 'g')
-    xcode = _sh_dtype_code(x_dtype, 'x_dtype')
-    K = _sh_params(weight, None, C)
-    _require_on_device(pooled, 'pooled')
-    if g.ndim != 2 or tuple(g.shape) != (B, K) or not g.is_contiguous() or min(B, C, H, W) < 1:
+    gcode = L.float_code_of_dtype(g.dtype, 'g')
+    xcode = L.float_code_of_dtype(x_dtype, 'x_dtype')
+    K, w_, _ = _sh_params(weight, None, C)
+    p_ = _f32(pooled, (B, C), 'pooled', dense=True)
+    if tuple(g.shape) != (B, K) or not g.is_contiguous() or min(B, C, H, W) < 1:
         raise TypeError(f'g must be contiguous [{B}, {K}] for a non-empty map, got {tuple(g.shape)}')
-    if pooled.dtype != torch.float32 or tuple(pooled.shape) != (B, C) or not pooled.is_contiguous():
-        raise TypeError(f'pooled must be contiguous float32 [{B}, {C}], got {pooled.dtype} {tuple(pooled.shape)}')
     gd = g.detach()
     dev = gd.device
     gx = torch.empty((B, C, H, W), dtype=x_dtype, device=dev) if need[0] else None
     gw = torch.empty((K, C), dtype=torch.float32, device=dev) if need[1] else None
     gb = torch.empty((K,), dtype=torch.float32, device=dev) if need[2] else None
-    L.check(L.lib().nmsa_scene_head_bwd(L.ptr(gd), gcode, L.ptr(pooled.detach()), L.ptr(weight.detach()), B, C, H, W,
-                                        K, L.ptr(gx), xcode, L.ptr(gw), L.ptr(gb), L.stream_ptr(dev)),
-            'nmsa_scene_head_bwd')
+    L.check(L.lib().nmsa_scene_head_bwd(L.ptr(gd), gcode, L.ptr(p_), L.ptr(w_), B, C, H, W, K, L.ptr(gx), xcode,
+                                        L.ptr(gw), L.ptr(gb), L.stream_ptr(dev)), 'nmsa_scene_head_bwd')
     return gx, gw, gb
 
 
@@ -2165,10 +2068,7 @@ def scene_head_route(x: torch.Tensor, n_classes: int = 1) -> int:
     if x.ndim != 4:
         raise ValueError('a [B, C, H, W] map')
     B, C, H, W = (int(n) for n in x.shape)
-    rc = L.lib().nmsa_scene_head_route(L.C.c_void_p(x.data_ptr()), L.float_dtype_code(x), B, C, H, W, int(n_classes))
-    if rc < 0:
-        L.check(rc, 'nmsa_scene_head_route')
-    return rc
+    return _route('nmsa_scene_head_route', x.data_ptr(), L.float_dtype_code(x), B, C, H, W, int(n_classes))
 
 
 # ------------------------------------------------------------- orientation MAE on device tables
