@@ -14,12 +14,9 @@ import pytest
 import torch
 
 from _golden import load, jload, ids_from_arrays, meta_from_arrays
+from _gpu_support import dev
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def make_batch(B, H, W, extra=None):

@@ -4,50 +4,18 @@ Round 4 found three kinds of silent regressions in the generated code, none of w
 result: register spills to scratch memory (100 B per lane were 8 % of the wide cross entropy's HBM
 writes), hundreds of loop-invariant scalar plane offsets spilled to lane registers, and hash-probe
 loops unrolled into 37 900 instructions.  This test compiles the three files that hold those
-kernels with LLVM's kernel-resource-usage remarks and checks the hot instantiations.
-(`tools/isa_survey.sh` prints the same survey for every kernel of the library.)"""
-import os
+kernels with LLVM's resource-usage remarks and checks the hot instantiations.  (The harness is
+tests/_codegen.py; `tools/isa_survey.sh` prints the same survey for every kernel of the library.)"""
 import re
-import shutil
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-
-
-def _usage(src, extra=()):
-    """{mangled kernel name: {'vgpr', 'scratch', 'sgpr_spill', 'occupancy'}} of one source file"""
-    out = subprocess.run([HIPCC, *FLAGS, *extra, src], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in (('vgpr', r' VGPRs: (\d+)'), ('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'),
-                         ('sgpr_spill', r'SGPRs Spill: (\d+)'), ('occupancy', r'Occupancy \[waves/SIMD\]: (\d+)')):
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+import _codegen
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    jobs = {'losses_split.hip': (), 'losses_cos.hip': (), 'metrics.hip': ()}
-    with ThreadPoolExecutor(max_workers=3) as pool:
-        res = dict(zip(jobs, pool.map(lambda kv: _usage(kv[0], kv[1]), jobs.items())))
-    return res
+    return _codegen.usage_many(('losses_split.hip', 'losses_cos.hip', 'metrics.hip'))
 
 
 def test_wide_cross_entropy_has_no_scratch(usage):

@@ -1,47 +1,16 @@
-"""CPU tier: code-generation guard for csrc/augment.hip, in the manner of
-tests/test_codegen_multiscale.py (hipcc cross-compiles without a GPU).  The augmentation kernel
-keeps its descriptor in scalar registers and at most the 12 source elements of four pixels per
-lane: scratch or spilled registers would mean the pixel array, indexed by the flip, went to
-memory."""
-import os
-import re
-import shutil
-import subprocess
-
+"""CPU tier: code-generation guard for csrc/augment.hip (the harness is tests/_codegen.py).  The
+augmentation kernel keeps its descriptor in scalar registers and at most the 12 source elements of
+four pixels per lane: scratch or spilled registers would mean the pixel array, indexed by the flip,
+went to memory."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-FIELDS = (('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)'),
-          ('vgpr_spill', r'VGPRs Spill: (\d+)'))
+import _codegen
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    out = subprocess.run([HIPCC, *FLAGS, 'augment.hip'], cwd=CSRC, capture_output=True, text=True,
-                         timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in FIELDS:
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+    return _codegen.usage('augment.hip')
 
 
 def test_augment_kernel_has_no_scratch_and_no_spills(usage):
-    found = {k: v for k, v in usage.items() if 'k_batch_augment' in k}
-    assert len(found) == 1, sorted(usage)              # one kernel for every mode and element size
-    for k, v in found.items():
-        assert v['scratch'] == 0 and v['sgpr_spill'] == 0 and v['vgpr_spill'] == 0, (k, v)
+    _codegen.assert_clean(usage, {'k_batch_augment': 1})    # one kernel for every mode and element size

@@ -1,43 +1,15 @@
-"""CPU tier: code-generation guard for csrc/encoder_fusion.hip, in the manner of
-tests/test_codegen_mlp_decoder.py (hipcc cross-compiles without a GPU).  The reduction kernels keep
-up to sixteen partial sums and two chunks of eight values per lane, the excite kernels carry eight
-parameter pointers in a by-value argument struct: scratch or spilled registers would mean one of them
-went to memory."""
-import os
-import re
-import shutil
-import subprocess
-
+"""CPU tier: code-generation guard for csrc/encoder_fusion.hip (the harness is tests/_codegen.py).
+The reduction kernels keep up to sixteen partial sums and two chunks of eight values per lane, the
+excite kernels carry eight parameter pointers in a by-value argument struct: scratch or spilled
+registers would mean one of them went to memory."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-FIELDS = (('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)'),
-          ('vgpr_spill', r'VGPRs Spill: (\d+)'))
+import _codegen
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    out = subprocess.run([HIPCC, *FLAGS, 'encoder_fusion.hip'], cwd=CSRC, capture_output=True, text=True,
-                         timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in FIELDS:
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+    return _codegen.usage('encoder_fusion.hip')
 
 
 def test_every_encoder_fusion_kernel_has_no_scratch_and_no_spills(usage):
@@ -45,8 +17,4 @@ def test_every_encoder_fusion_kernel_has_no_scratch_and_no_spills(usage):
     # (VECTOR, ELEMENT); the excite kernels: ReLU, SiLU
     stems = {'k_sefuse_squeeze': 12, 'k_sefuse_wgrad': 12, 'k_sefuse_scale_add': 6, 'k_sefuse_apply': 6,
              'k_sefuse_exciteI': 2, 'k_sefuse_excite_bwd': 2}
-    count = {stem: sum(stem in k for k in usage) for stem in stems}
-    assert count == stems, sorted(usage)
-    assert len(usage) == sum(stems.values()), sorted(usage)
-    for k, v in usage.items():
-        assert v == {'scratch': 0, 'sgpr_spill': 0, 'vgpr_spill': 0}, (k, v)
+    _codegen.assert_clean(usage, stems, whole_file=True)

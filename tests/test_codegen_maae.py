@@ -1,41 +1,14 @@
-"""CPU tier: code-generation guard for csrc/maae.hip, in the manner of tests/test_codegen_normal.py
-(hipcc cross-compiles without a GPU).  Both kernels are one latency-bound workgroup; the matched
-one keeps its table descriptors in LDS so that nothing spills."""
-import os
-import re
-import shutil
-import subprocess
-
+"""CPU tier: code-generation guard for csrc/maae.hip (the harness is tests/_codegen.py).  Both
+kernels are one latency-bound workgroup; the matched one keeps its table descriptors in LDS so that
+nothing spills."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-FIELDS = (('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)'),
-          ('vgpr_spill', r'VGPRs Spill: (\d+)'))
+import _codegen
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    out = subprocess.run([HIPCC, *FLAGS, 'maae.hip'], cwd=CSRC, capture_output=True, text=True,
-                         timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in FIELDS:
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+    return _codegen.usage('maae.hip')
 
 
 def test_the_file_holds_exactly_the_two_kernels(usage):
@@ -44,7 +17,4 @@ def test_the_file_holds_exactly_the_two_kernels(usage):
 
 @pytest.mark.parametrize('kernel', ['k_maae_keyed', 'k_maae_matched'])
 def test_kernels_have_no_scratch_and_no_spills(usage, kernel):
-    found = {k: v for k, v in usage.items() if kernel in k}
-    assert len(found) == 1, sorted(usage)               # one instantiation each
-    for k, v in found.items():
-        assert v['scratch'] == 0 and v['sgpr_spill'] == 0 and v['vgpr_spill'] == 0, (k, v)
+    _codegen.assert_clean(usage, {kernel: 1})               # one instantiation each

@@ -1,48 +1,17 @@
-"""CPU tier: code-generation guard for csrc/maxpool.hip, in the manner of tests/test_codegen_block.py (hipcc
-cross-compiles without a GPU).  The forward kernel keeps three scanned rows of up to four (value, bits, position)
-choices per lane, the backward kernel two window rows of five gradients and codes and eight sums: scratch or
-spilled registers would mean one of them went to memory."""
-import os
-import re
-import shutil
-import subprocess
-
+"""CPU tier: code-generation guard for csrc/maxpool.hip (the harness is tests/_codegen.py).  The forward kernel
+keeps three scanned rows of up to four (value, bits, position) choices per lane, the backward kernel two window
+rows of five gradients and codes and eight sums: scratch or spilled registers would mean one of them went to
+memory."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-FIELDS = (('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)'),
-          ('vgpr_spill', r'VGPRs Spill: (\d+)'))
+import _codegen
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    out = subprocess.run([HIPCC, *FLAGS, 'maxpool.hip'], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in FIELDS:
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+    return _codegen.usage('maxpool.hip')
 
 
 def test_every_maxpool_kernel_has_no_scratch_and_no_spills(usage):
     # forward and backward: 3 dtypes x (VECTOR, PIXEL)
-    stems = {'k_mp_fwd': 6, 'k_mp_bwd': 6}
-    count = {stem: sum(stem in k for k in usage) for stem in stems}
-    assert count == stems, sorted(usage)
-    assert len(usage) == sum(stems.values()), sorted(usage)
-    for k, v in usage.items():
-        assert v == {'scratch': 0, 'sgpr_spill': 0, 'vgpr_spill': 0}, (k, v)
+    _codegen.assert_clean(usage, {'k_mp_fwd': 6, 'k_mp_bwd': 6}, whole_file=True)

@@ -1,50 +1,17 @@
-"""CPU tier: code-generation guard for csrc/mlp_decoder.hip, in the manner of
-tests/test_codegen_context_module.py (hipcc cross-compiles without a GPU).  The kernels carry the
-per-branch channel counts, shifts and pointers in a by-value argument struct and pick a branch with
-fully unrolled selects inside a grid-stride loop: scratch or spilled registers would mean the struct
-(or a lane's vector of results) went to memory."""
-import os
-import re
-import shutil
-import subprocess
-
+"""CPU tier: code-generation guard for csrc/mlp_decoder.hip (the harness is tests/_codegen.py).  The
+kernels carry the per-branch channel counts, shifts and pointers in a by-value argument struct and
+pick a branch with fully unrolled selects inside a grid-stride loop: scratch or spilled registers
+would mean the struct (or a lane's vector of results) went to memory."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-FIELDS = (('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)'),
-          ('vgpr_spill', r'VGPRs Spill: (\d+)'))
+import _codegen
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    out = subprocess.run([HIPCC, *FLAGS, 'mlp_decoder.hip'], cwd=CSRC, capture_output=True, text=True,
-                         timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in FIELDS:
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+    return _codegen.usage('mlp_decoder.hip')
 
 
 def test_every_mlp_decoder_kernel_has_no_scratch_and_no_spills(usage):
     # 3 dtypes x (VECTOR, ELEMENT) of the forward kernel, 3 dtypes of the backward kernel
-    stems = ('k_mlpdec_upcat_fwd', 'k_mlpdec_upcat_bwd')
-    count = {stem: sum(stem in k for k in usage) for stem in stems}
-    assert count == {'k_mlpdec_upcat_fwd': 6, 'k_mlpdec_upcat_bwd': 3}, sorted(usage)
-    assert len(usage) == 9, sorted(usage)
-    for k, v in usage.items():
-        assert v == {'scratch': 0, 'sgpr_spill': 0, 'vgpr_spill': 0}, (k, v)
+    _codegen.assert_clean(usage, {'k_mlpdec_upcat_fwd': 6, 'k_mlpdec_upcat_bwd': 3}, whole_file=True)

@@ -1,46 +1,17 @@
-"""CPU tier: code-generation guard for csrc/normal.hip, in the manner of tests/test_codegen_dve.py
-(hipcc cross-compiles without a GPU).  Both kernels are streaming passes with a handful of live
-values per lane; scratch or spilled registers would add memory traffic to a memory-bound pass."""
-import os
-import re
-import shutil
-import subprocess
-
+"""CPU tier: code-generation guard for csrc/normal.hip (the harness is tests/_codegen.py).  Both
+kernels are streaming passes with a handful of live values per lane; scratch or spilled registers
+would add memory traffic to a memory-bound pass."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-FIELDS = (('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)'),
-          ('vgpr_spill', r'VGPRs Spill: (\d+)'))
+import _codegen
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    out = subprocess.run([HIPCC, *FLAGS, 'normal.hip'], cwd=CSRC, capture_output=True, text=True,
-                         timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in FIELDS:
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+    return _codegen.usage('normal.hip')
 
 
 @pytest.mark.parametrize('kernel, variants', [('k_normal_valid_mask', 2), ('k_rmse', 36)])
 def test_kernels_have_no_scratch_and_no_spills(usage, kernel, variants):
-    found = {k: v for k, v in usage.items() if kernel in k}
-    assert len(found) == variants, sorted(usage)   # mask: vector / scalar; rmse: 3 dtypes x 3 masks x 2 sources x 2
-    for k, v in found.items():
-        assert v['scratch'] == 0 and v['sgpr_spill'] == 0 and v['vgpr_spill'] == 0, (k, v)
+    # mask: vector / scalar; rmse: 3 dtypes x 3 masks x 2 sources x 2
+    _codegen.assert_clean(usage, {kernel: variants})

@@ -1,49 +1,18 @@
-"""CPU tier: code-generation guard for the orientation paint kernel of csrc/targets.hip, in the
-manner of tests/test_codegen_normal.py (hipcc cross-compiles without a GPU).  The paint is a
-streaming pass (4 B/px read, 9 B/px written) with a handful of live values per lane; scratch or
-spilled registers would add memory traffic to a memory-bound pass."""
-import os
-import re
-import shutil
-import subprocess
-
+"""CPU tier: code-generation guard for the orientation paint kernel of csrc/targets.hip (the harness
+is tests/_codegen.py).  The paint is a streaming pass (4 B/px read, 9 B/px written) with a handful
+of live values per lane; scratch or spilled registers would add memory traffic to a memory-bound
+pass."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nicr_mt_scene_analysis_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wno-unused-function',
-         '--offload-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', os.devnull]
-FIELDS = (('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)'),
-          ('vgpr_spill', r'VGPRs Spill: (\d+)'))
+import _codegen
+
+VARIANTS = 4        # (on-wire 16-byte accesses | per-pixel) x (probe of the scan's id table | binary search in LDS)
 
 
 @pytest.fixture(scope='module')
 def usage():
-    if not os.path.exists(HIPCC):
-        pytest.skip('hipcc not available')
-    out = subprocess.run([HIPCC, *FLAGS, 'targets.hip'], cwd=CSRC, capture_output=True, text=True,
-                         timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark:\s+Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        for key, pat in FIELDS:
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
+    return _codegen.usage('targets.hip')
 
 
 def test_paint_kernel_has_no_scratch_and_no_spills(usage):
-    found = {k: v for k, v in usage.items() if 'k_ot_paint' in k}
-    assert len(found) == VARIANTS, sorted(usage)
-    for k, v in found.items():
-        assert v['scratch'] == 0 and v['sgpr_spill'] == 0 and v['vgpr_spill'] == 0, (k, v)
-
-
-VARIANTS = 4        # (on-wire 16-byte accesses | per-pixel) x (probe of the scan's id table | binary search in LDS)
+    _codegen.assert_clean(usage, {'k_ot_paint': VARIANTS})

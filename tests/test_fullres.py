@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from _golden import load, jload
+from _gpu_support import dev
 from nicr_mt_scene_analysis_amd.testing import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +21,6 @@ def ops():
     assert torch.cuda.is_available(), 'needs the MI355X'
     from nicr_mt_scene_analysis_amd import ops as o
     return o
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _geoms(g):

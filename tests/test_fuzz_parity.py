@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from _golden import ids_from_arrays
+from _gpu_support import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +31,6 @@ _EFFECTIVE = {}
 
 def _n(examples):
     return examples * _SCALE
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @st.composite

@@ -46,8 +46,6 @@ follows in which only `rest` != 0 workgroups have an item):
   csrc/upsampling.hip   an item is 256 lane units of one plane, items = B * C * chunks.  B = 2, C = 13,
       9x8 (vector route) and 9x7 (one-pixel route): 26 items, cap 8: 3 trips + 2 workgroups.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -60,6 +58,7 @@ from nicr_mt_scene_analysis_amd.testing import mlp_decoder_ref as RM
 from nicr_mt_scene_analysis_amd.testing import synthetic as syn
 from nicr_mt_scene_analysis_amd.testing import upsampling_ref as RU
 
+from _gpu_support import assume_cus  # noqa: F401
 import test_context_module as TC
 import test_fusion as TF
 import test_mlp_decoder as TM
@@ -91,28 +90,6 @@ def cdiv(a, b):
 
 
 # ------------------------------------------------------------------------------ the switch
-@pytest.fixture
-def assume_cus():
-    """NMSA_ASSUME_CUS (read by the library at every call), restored afterwards.  set_cus(n) -> the
-    compute units the library sizes its grids from now; None: the device's own count"""
-    saved = os.environ.get('NMSA_ASSUME_CUS')
-    own = torch.cuda.get_device_properties(0).multi_processor_count
-
-    def set_cus(n):
-        if n is None:
-            os.environ.pop('NMSA_ASSUME_CUS', None)
-        else:
-            os.environ['NMSA_ASSUME_CUS'] = str(n)
-        cus = L.device_geometry()[0]
-        assert cus == (own if n is None else n), 'the library does not follow NMSA_ASSUME_CUS'
-        return cus
-    yield set_cus
-    if saved is None:
-        os.environ.pop('NMSA_ASSUME_CUS', None)
-    else:
-        os.environ['NMSA_ASSUME_CUS'] = saved
-
-
 def trips(items, per_cu, cus):
     """(workgroups, trips every workgroup makes, workgroups with an item in the trip after those)"""
     grid = min(items, per_cu * cus)

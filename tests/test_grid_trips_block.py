@@ -15,14 +15,14 @@ Items (B = 2, C = 53: 106 planes):
       cap 24: 2 + 5.
   the reduction that finishes alone: 53 items (channels), barriers inside, cap 8: 6 + 5, cap 24: 2 + 5.
 """
-import os
-
 import pytest
 import torch
 
 from nicr_mt_scene_analysis_amd import _lib as L
 from nicr_mt_scene_analysis_amd import ops
 from nicr_mt_scene_analysis_amd.testing import block_ref as R
+
+from _gpu_support import assume_cus  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -37,26 +37,6 @@ EPS, MOM = 1e-5, 0.1
 
 def cdiv(a, b):
     return -(-a // b)
-
-
-@pytest.fixture
-def assume_cus():
-    saved = os.environ.get('NMSA_ASSUME_CUS')
-    own = torch.cuda.get_device_properties(0).multi_processor_count
-
-    def set_cus(n):
-        if n is None:
-            os.environ.pop('NMSA_ASSUME_CUS', None)
-        else:
-            os.environ['NMSA_ASSUME_CUS'] = str(n)
-        cus = L.device_geometry()[0]
-        assert cus == (own if n is None else n), 'the library does not follow NMSA_ASSUME_CUS'
-        return cus
-    yield set_cus
-    if saved is None:
-        os.environ.pop('NMSA_ASSUME_CUS', None)
-    else:
-        os.environ['NMSA_ASSUME_CUS'] = saved
 
 
 def assert_trips(items, what):

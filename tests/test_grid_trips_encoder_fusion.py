@@ -17,14 +17,14 @@ Items (B = 2, C = 53: 106 planes, no multiple of the four planes of a WAVE-route
       route) or one (ELEMENT route) of the flat tensor of 407040 elements (48x80): 100 / 50 / 398 items,
       cap 8: 12 + 4 / 6 + 2 / 49 + 6, cap 24: 4 + 4 / 2 + 2 / 16 + 14.
 """
-import os
-
 import pytest
 import torch
 
 from nicr_mt_scene_analysis_amd import _lib as L
 from nicr_mt_scene_analysis_amd import ops
 from nicr_mt_scene_analysis_amd.testing import encoder_fusion_ref as R
+
+from _gpu_support import assume_cus  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -41,26 +41,6 @@ WAVE_HW, BLOCK_HW = (15, 20), (48, 80)
 
 def cdiv(a, b):
     return -(-a // b)
-
-
-@pytest.fixture
-def assume_cus():
-    saved = os.environ.get('NMSA_ASSUME_CUS')
-    own = torch.cuda.get_device_properties(0).multi_processor_count
-
-    def set_cus(n):
-        if n is None:
-            os.environ.pop('NMSA_ASSUME_CUS', None)
-        else:
-            os.environ['NMSA_ASSUME_CUS'] = str(n)
-        cus = L.device_geometry()[0]
-        assert cus == (own if n is None else n), 'the library does not follow NMSA_ASSUME_CUS'
-        return cus
-    yield set_cus
-    if saved is None:
-        os.environ.pop('NMSA_ASSUME_CUS', None)
-    else:
-        os.environ['NMSA_ASSUME_CUS'] = saved
 
 
 def assert_trips(items, per_cu, what):

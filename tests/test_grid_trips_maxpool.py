@@ -13,14 +13,14 @@ Items (B = 2, C = 53: 106 planes):
   vector route, 81x48 (float32) / 81x96 (half): Ho = 41, 6 tiles x 12 groups = 72 units a plane, 7632 units,
       30 items; cap 8: 3 + 6, cap 24: 1 + 6; the last item holds 208 units.
 """
-import os
-
 import pytest
 import torch
 
 from nicr_mt_scene_analysis_amd import _lib as L
 from nicr_mt_scene_analysis_amd import ops
 from nicr_mt_scene_analysis_amd.testing import maxpool_ref as R
+
+from _gpu_support import assume_cus  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -35,26 +35,6 @@ B, C = 2, 53
 
 def cdiv(a, b):
     return -(-a // b)
-
-
-@pytest.fixture
-def assume_cus():
-    saved = os.environ.get('NMSA_ASSUME_CUS')
-    own = torch.cuda.get_device_properties(0).multi_processor_count
-
-    def set_cus(n):
-        if n is None:
-            os.environ.pop('NMSA_ASSUME_CUS', None)
-        else:
-            os.environ['NMSA_ASSUME_CUS'] = str(n)
-        cus = L.device_geometry()[0]
-        assert cus == (own if n is None else n), 'the library does not follow NMSA_ASSUME_CUS'
-        return cus
-    yield set_cus
-    if saved is None:
-        os.environ.pop('NMSA_ASSUME_CUS', None)
-    else:
-        os.environ['NMSA_ASSUME_CUS'] = saved
 
 
 def assert_trips(items):

@@ -4,42 +4,19 @@ and walks the rest in a loop; with ONE compute unit assumed (`NMSA_ASSUME_CUS`, 
 call) the cap is 8 workgroups.  At (2, 66, 7, 37, 45) there are 132 plane items, 47 gweight items and one gbias
 item: 45 workgroup trips' worth, so every workgroup runs five or six trips and the three kinds of items meet
 inside one workgroup.  The results must be the bits the device's own count gives, and the restatement's."""
-import os
-
 import pytest
 import torch
 
-from nicr_mt_scene_analysis_amd import _lib as L
 from nicr_mt_scene_analysis_amd import ops
 from nicr_mt_scene_analysis_amd.testing import scene_head_ref as R
+
+from _gpu_support import assume_cus  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device('cuda:0')
 SHAPE = (2, 66, 7, 37, 45)
 WAVES_PER_WORKGROUP, WORKGROUPS_PER_CU = 4, 8
-
-
-@pytest.fixture
-def assume_cus():
-    """NMSA_ASSUME_CUS, restored afterwards.  set_cus(n) -> the compute units the library sizes its grids from
-    now; None: the device's own count"""
-    saved = os.environ.get('NMSA_ASSUME_CUS')
-    own = torch.cuda.get_device_properties(0).multi_processor_count
-
-    def set_cus(n):
-        if n is None:
-            os.environ.pop('NMSA_ASSUME_CUS', None)
-        else:
-            os.environ['NMSA_ASSUME_CUS'] = str(n)
-        cus = L.device_geometry()[0]
-        assert cus == (own if n is None else n), 'the library does not follow NMSA_ASSUME_CUS'
-        return cus
-    yield set_cus
-    if saved is None:
-        os.environ.pop('NMSA_ASSUME_CUS', None)
-    else:
-        os.environ['NMSA_ASSUME_CUS'] = saved
 
 
 @pytest.mark.parametrize('dtype', (torch.float32, torch.bfloat16, torch.float16), ids=str)

@@ -18,8 +18,6 @@ can overflow: an average pool and a resize are convex combinations of their inpu
 Module level: the fused path and the torch path of the three residual blocks and of the 'se-add' fusion answer
 one poisoned input with the same classes; `GradScaler` skips the step behind an infinite gradient.
 """
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -38,6 +36,7 @@ from nicr_mt_scene_analysis_amd.testing import mlp_decoder_ref as RM
 from nicr_mt_scene_analysis_amd.testing import nonfinite as NF
 from nicr_mt_scene_analysis_amd.testing import upsampling_ref as RU
 
+from _gpu_support import assume_cus  # noqa: F401
 import test_block as TB
 import test_encoder_fusion as TE
 
@@ -170,29 +169,6 @@ DTYPE_IDS = {F32: 'f32', BF16: 'bf16', F16: 'f16'}
 def _params(cases, dtypes):
     return [pytest.param(c, dt, id=f"{c.id}-{'-'.join(DTYPE_IDS[t] for t in dt) if isinstance(dt, tuple) else DTYPE_IDS[dt]}")
             for c in cases for dt in dtypes]
-
-
-# ------------------------------------------------------------------------------ the switch (tests/test_grid_trips.py)
-@pytest.fixture
-def assume_cus():
-    """NMSA_ASSUME_CUS (read by the library at every call), restored afterwards.  set_cus(n) -> the
-    compute units the library sizes its grids from now; None: the device's own count"""
-    saved = os.environ.get('NMSA_ASSUME_CUS')
-    own = torch.cuda.get_device_properties(0).multi_processor_count
-
-    def set_cus(n):
-        if n is None:
-            os.environ.pop('NMSA_ASSUME_CUS', None)
-        else:
-            os.environ['NMSA_ASSUME_CUS'] = str(n)
-        cus = L.device_geometry()[0]
-        assert cus == (own if n is None else n), 'the library does not follow NMSA_ASSUME_CUS'
-        return cus
-    yield set_cus
-    if saved is None:
-        os.environ.pop('NMSA_ASSUME_CUS', None)
-    else:
-        os.environ['NMSA_ASSUME_CUS'] = saved
 
 
 # ------------------------------------------------------------------------------ one poison, one input

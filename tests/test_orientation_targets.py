@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from _golden import load, jload
+from _gpu_support import dev
 from _orientation_ref import (assert_bits_equal, pack_keys, paint_present, random_angles, restate,
                               ulp_distance)
 from nicr_mt_scene_analysis_amd.testing import synthetic as syn
@@ -50,10 +51,6 @@ def check_against_fixture(name, ori, fg, present, inp, want):
     assert [list(p.items()) for p in present] == [list(p.items()) for p in want['present']], name
     assert_bits_equal(ori, paint_present(inp['instance'], want['present']), name)
     assert ulp_distance(ori, want['orientation']).max() <= 1, name
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def run_ops(sem_t, ins_t, n_classes, estimate, orientations, max_instances=1024):

@@ -11,13 +11,10 @@ import pytest
 import torch
 
 from _golden import load, ids_from_arrays
+from _gpu_support import dev
 from nicr_mt_scene_analysis_amd.testing import synthetic as syn
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _stuff_lut(is_thing):

@@ -23,6 +23,7 @@ import pytest
 import torch
 
 from _golden import ids_from_arrays
+from _gpu_support import dev
 from _orientation_ref import assert_bits_equal, pack_keys, random_angles, restate
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +31,6 @@ pytestmark = pytest.mark.gpu
 SCAN, FAST, TILED, VECTOR, LUT_LDS, SCAN_16 = 1, 2, 4, 8, 16, 32
 TORCH_OF = {np.uint8: torch.uint8, np.int16: torch.int16, np.int32: torch.int32, np.int64: torch.int64}
 MAX_PER_CAT = 1 << 16
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def want_route(kind, sigma, max_inst):
