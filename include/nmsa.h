@@ -1582,6 +1582,53 @@ int nmsa_scene_head_fwd(const void* x, int dtype_x, int B, int C, int H, int W, 
 int nmsa_scene_head_bwd(const void* g, int dtype_g, const float* pooled, const float* weight, int B, int C, int H,
                         int W, int K, void* gx, int dtype_x, float* gweight, float* gbias, nmsa_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * dense decoders: x2 upsampling and the addition of the encoder skip (csrc/up_add.hip)
+ *     model/decoder/dense_base.py: the end of every decoder module, `Upsampling` (x2), and the `add` of
+ *     model/encoder_decoder_fusion.py that follows it (torch: an upsampling pass and an addition pass).
+ *
+ *   y[n,c,Y,X] = u[n,c,Y,X] + skip[n,c,Y,X],   u = up(x)
+ *   x          [B,C,h,w]    NMSA_F32 | NMSA_BF16 | NMSA_F16, contiguous; ONE dtype per call
+ *   skip, y    [B,C,2h,2w]  the same dtype, contiguous
+ *   weight f32 [C,1,3,3], bias f32 [C] (may be NULL: no bias): read in the two learned modes only
+ *   mode  NMSA_UPADD_NEAREST          u = x[n,c,Y>>1,X>>1]: y is one IEEE addition
+ *         NMSA_UPADD_BILINEAR         ATen's align_corners = False rule at scale 0.5 (source indices and
+ *                                     weights of every output row and column as ATen computes them, the
+ *                                     blend (a*wx0 + b*wx1)*wy0 + (c*wx0 + d*wx1)*wy1 with one fused
+ *                                     multiply-add per sum).  A clamped border tap is multiplied by its
+ *                                     zero weight: an infinity next to the border gives ATen's NaN.
+ *         NMSA_UPADD_LEARNED          u of nmsa_upsample2x_dw3x3_fwd with zeropad = 0: the same formula,
+ *         NMSA_UPADD_LEARNED_ZEROPAD  halo rules and operation order; with zeropad = 1
+ *   Everything is float32 inside; a half output is rounded once, to nearest even, AFTER the addition
+ *   (the composition rounds u as well).
+ *
+ * nmsa_up2x_add_fwd: ONE launch, x and skip read once, y written once; no workspace, no atomics.  There
+ *   is no backward entry point: the gradient of skip is the upstream gradient itself, the gradient of x
+ *   (weight, bias) is that of the upsampling alone (nmsa_upsample2x_dw3x3_bwd; nmsa_mlpdec_upcat_bwd with
+ *   one branch of factor 2 for nearest / bilinear).
+ * nmsa_up2x_add_route (host only, nothing is launched, no device is touched): the route the forward call
+ *   takes with these tensors.  NMSA_UPADD_ROUTE_VECTOR: a lane owns 2 (f32) or 4 (half) consecutive input
+ *   pixels and moves 16-byte vectors of skip and y; taken when w % 2 == 0 (f32) / w % 4 == 0 (half) and x,
+ *   skip and y all start on 16 bytes.  NMSA_UPADD_ROUTE_PIXEL: one input pixel per lane, element-wise
+ *   accesses, any width and any element-aligned pointer.  Both routes give the same bits.
+ *
+ * Everything is checked before anything is enqueued, with or without a device.  NMSA_ERR_ARG: a NULL
+ * x / skip / y, a NULL weight in a learned mode, a dtype other than the three, a mode other than the
+ * four, B, C, h or w below 1, a pointer that is not aligned to its element, a y whose bytes overlap
+ * those of x or skip.  NMSA_ERR_UNSUPPORTED: a single output plane of 2^31 elements or more (4hw; offsets
+ * inside a plane are 32-bit, the plane base is 64-bit, so B*C*4hw may exceed 2^31), B*C above 2^31 - 1,
+ * 2^31 or more workgroup items.  No host synchronisation, no allocation; capturable in a hipGraph.
+ * ------------------------------------------------------------------------- */
+#define NMSA_UPADD_NEAREST 0
+#define NMSA_UPADD_BILINEAR 1
+#define NMSA_UPADD_LEARNED 2
+#define NMSA_UPADD_LEARNED_ZEROPAD 3
+#define NMSA_UPADD_ROUTE_VECTOR 1
+#define NMSA_UPADD_ROUTE_PIXEL 2
+int nmsa_up2x_add_route(const void* x, const void* skip, const void* y, int dtype, int B, int C, int h, int w);
+int nmsa_up2x_add_fwd(const void* x, int dtype, int mode, const float* weight, const float* bias,
+                      const void* skip, int B, int C, int h, int w, void* y, nmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

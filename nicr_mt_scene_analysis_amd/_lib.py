@@ -56,6 +56,9 @@ NMSA_MP_ROUTE_VECTOR, NMSA_MP_ROUTE_PIXEL = 1, 2
 # include/nmsa.h: channel limit and route answers of the nmsa_scene_head_* entry points
 NMSA_SCENE_HEAD_MAX_CHANNELS = 2048
 NMSA_SH_ROUTE_UNIT, NMSA_SH_ROUTE_VECTOR, NMSA_SH_ROUTE_ELEMENT = 1, 2, 4
+# include/nmsa.h: modes and route answers of the nmsa_up2x_add_* entry points
+NMSA_UPADD_NEAREST, NMSA_UPADD_BILINEAR, NMSA_UPADD_LEARNED, NMSA_UPADD_LEARNED_ZEROPAD = 0, 1, 2, 3
+NMSA_UPADD_ROUTE_VECTOR, NMSA_UPADD_ROUTE_PIXEL = 1, 2
 
 
 class NmsaError(RuntimeError):
@@ -172,6 +175,8 @@ _SIGNATURES = {
     'nmsa_scene_head_route': (_i, [_vp, _i, _i, _i, _i, _i, _i]),
     'nmsa_scene_head_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     'nmsa_scene_head_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    'nmsa_up2x_add_route': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    'nmsa_up2x_add_fwd': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'nmsa_instance_orientation_wide': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     'nmsa_instance_orientation': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

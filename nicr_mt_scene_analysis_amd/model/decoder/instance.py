@@ -1,5 +1,7 @@
-"""Instance MLP decoder and its head (reference model/decoder/instance.py, `InstanceHead`,
-`InstanceMLPDecoder`).  The head is plain torch; its 'learned-3x3' upsamplings run on HIP."""
+"""Instance decoders and their head (reference model/decoder/instance.py, `InstanceHead`, the convolutional
+`InstanceDecoder` over `DenseDecoderBase`, `InstanceMLPDecoder`).
+The head is plain torch; its 'learned-3x3' upsamplings run on HIP."""
+from math import log2
 from typing import Optional, Tuple, Type
 
 import torch
@@ -7,12 +9,14 @@ from torch import Tensor, nn
 
 from ...utils import OrientationOutputNormalization
 from ..activation import get_activation_class
+from ..block import BlockType
 from ..encoder_decoder_fusion import EncoderDecoderFusionType
 from ..normalization import get_normalization_class
 from ..postprocessing import get_postprocessing_class
 from ..upsampling import UpsamplingType
 from ..upsampling import get_upsampling_class
 from ..utils import ConvNormAct
+from .dense_base import DenseDecoderBase
 from .mlp_base import MLPDecoderBase
 
 
@@ -62,6 +66,53 @@ class InstanceHead(nn.Module):
         if self._n_tasks == 3:
             outs[2] = self._act_orientation(outs[2])
         return tuple(outs)
+
+
+class InstanceDecoder(DenseDecoderBase):
+    def __init__(
+        self,
+        n_channels_in: int,
+        downsampling_in: int,
+        n_channels: Tuple[int, ...],
+        downsamplings: Tuple[int, ...],
+        block: Type[BlockType],
+        n_blocks: int,
+        fusion: Type[EncoderDecoderFusionType],
+        fusion_n_channels: Tuple[int, ...],
+        fusion_downsamplings: Tuple[int, ...],
+        n_channels_per_task: int = 32,
+        with_orientation: bool = False,
+        sigmoid_for_center: bool = True,
+        tanh_for_offset: bool = True,
+        postprocessing: Type = get_postprocessing_class('instance'),
+        normalization: Type[nn.Module] = get_normalization_class(),
+        activation: Type[nn.Module] = get_activation_class(),
+        upsampling: Type[UpsamplingType] = get_upsampling_class(),
+        prediction_upsampling: Type[UpsamplingType] = get_upsampling_class()
+    ) -> None:
+        super().__init__(n_channels_in=n_channels_in, downsampling_in=downsampling_in, n_channels=n_channels,
+                         downsamplings=downsamplings, block=block, n_blocks=n_blocks, fusion=fusion,
+                         fusion_n_channels=fusion_n_channels, fusion_downsamplings=fusion_downsamplings,
+                         postprocessing=postprocessing, normalization=normalization, activation=activation,
+                         upsampling=upsampling)
+
+        def head(n_channels_in, upsampling, n_upsamplings):
+            return InstanceHead(n_channels_in=n_channels_in, n_channels_per_task=n_channels_per_task,
+                                with_orientation=with_orientation, sigmoid_for_center=sigmoid_for_center,
+                                tanh_for_offset=tanh_for_offset, normalization=normalization, activation=activation,
+                                upsampling=upsampling, n_upsamplings=n_upsamplings)
+
+        # the main head upsamples to the input resolution; a side head stays at its own scale
+        self._task_head = head(n_channels[-1], prediction_upsampling, int(log2(downsamplings[-1])))
+        self._side_output_heads = nn.ModuleList(head(n, None, 0) for n in self.side_output_n_channels)
+
+    @property
+    def task_head(self) -> nn.Module:
+        return self._task_head
+
+    @property
+    def side_output_heads(self) -> nn.ModuleList:
+        return self._side_output_heads
 
 
 class InstanceMLPDecoder(MLPDecoderBase):

@@ -1637,6 +1637,60 @@ def mlpdec_route(ys, out: torch.Tensor) -> int:
                   _int_array(shifts))
 
 
+# ------------------------------------------------ dense decoders: x2 upsampling + skip add in one launch
+_UPADD_MODES = {'nearest': L.NMSA_UPADD_NEAREST, 'bilinear': L.NMSA_UPADD_BILINEAR,
+                'learned-3x3': L.NMSA_UPADD_LEARNED, 'learned-3x3-zeropad': L.NMSA_UPADD_LEARNED_ZEROPAD}
+
+
+def _upadd_shapes(x: torch.Tensor, skip: torch.Tensor) -> Tuple[int, int, int, int]:
+    """(B, C, h, w) of x; a skip that is not a [B, C, 2h, 2w] map is a ValueError"""
+    B, C, h, w = (int(n) for n in x.shape)
+    if tuple(skip.shape) != (B, C, 2 * h, 2 * w):
+        raise ValueError(f'skip must be [{B}, {C}, {2 * h}, {2 * w}] for x {tuple(x.shape)}, got {tuple(skip.shape)}')
+    return B, C, h, w
+
+
+def up2x_add(x: torch.Tensor, skip: torch.Tensor, mode: str, weight: Optional[torch.Tensor] = None,
+             bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`Upsampling(mode)(x) + skip` of the dense decoder modules in one launch (include/nmsa.h
+    nmsa_up2x_add_fwd): `x` [B, C, h, w] and `skip` [B, C, 2h, 2w] of one dtype (float32 / bfloat16 / float16) on
+    the device, made contiguous when they are not.  `mode` 'nearest', 'bilinear' (align_corners=False),
+    'learned-3x3' or 'learned-3x3-zeropad'; the learned modes take `weight` float32 [C, 1, 3, 3] and `bias`
+    float32 [C] or None, the other two ignore both.  Float32 inside, a half result is rounded once, after the
+    addition.  Returns y [B, C, 2h, 2w] in x's dtype, written into `out` when a contiguous tensor of that shape
+    and dtype is given (it must not overlap x or skip).  No autograd: that is
+    `model.decoder.UpsampleAddFunction`."""
+    m = _choice(mode, _UPADD_MODES, 'mode')
+    if x.is_cuda and (x.ndim != 4 or x.numel() == 0):
+        raise ValueError(f'x must be a non-empty [B, C, h, w] tensor, got shape {tuple(x.shape)}')
+    code = _float_map(x, 'x')
+    _require_on_device(skip, 'skip')
+    B, C, h, w = _upadd_shapes(x, skip)
+    learned = m in (L.NMSA_UPADD_LEARNED, L.NMSA_UPADD_LEARNED_ZEROPAD)
+    if learned and weight is None:
+        raise TypeError(f"mode '{mode}' needs a weight")
+    w_ = _f32(weight, (C, 1, 3, 3), 'weight') if learned else None
+    b_ = _f32(bias, (C,), 'bias') if learned else None
+    xc = x.detach().contiguous()
+    sc = _like(skip, (B, C, 2 * h, 2 * w), xc.dtype, xc.device, 'skip')
+    y = _out(out, (B, C, 2 * h, 2 * w), xc.dtype, xc.device)
+    L.check(L.lib().nmsa_up2x_add_fwd(
+        L.ptr(xc), code, m, L.ptr(w_), L.ptr(b_), L.ptr(sc), B, C, h, w, L.ptr(y), L.stream_ptr(xc.device)),
+        'nmsa_up2x_add_fwd')
+    return y
+
+
+def up2x_add_route(x: torch.Tensor, skip: torch.Tensor, y: torch.Tensor) -> int:
+    """The route `up2x_add` takes with these tensors (`nmsa_up2x_add_route`): L.NMSA_UPADD_ROUTE_VECTOR (w a
+    multiple of 2 float32 / 4 half pixels and x, skip and y on 16 bytes) or L.NMSA_UPADD_ROUTE_PIXEL.  Only
+    shapes, the dtype and the addresses are looked at, nothing is launched."""
+    if x.ndim != 4:
+        raise ValueError(f'x must be [B, C, h, w], got shape {tuple(x.shape)}')
+    B, C, h, w = _upadd_shapes(x, skip)
+    return _route('nmsa_up2x_add_route', x.data_ptr(), skip.data_ptr(), y.data_ptr(), L.float_dtype_code(x),
+                  B, C, h, w)
+
+
 # ------------------------------------------------------- encoder RGB-D fusion: SE-weighted add
 _SEFUSE_ACTS = {'relu': L.NMSA_SEFUSE_ACT_RELU, 'silu': L.NMSA_SEFUSE_ACT_SILU}
 
