@@ -1037,6 +1037,67 @@ int nmsa_batch_augment(void* staging_host, void* staging_device, int n_desc, int
                        int n_words, nmsa_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * batch augmentation behind a resize (csrc/augment_resize.hip)
+ *
+ * nmsa_batch_augment_resized: the chain of nmsa_batch_augment behind RandomResize
+ *   (data/preprocessing/resize.py:311-340) or behind RandomCrop's upscale of an image smaller
+ *   than the crop (crop.py:43-55), in ONE launch that never forms the resized image: only the
+ *   pixels of the crop window are resampled.  `rgb` is resized with cv2.INTER_LINEAR, everything
+ *   else with cv2.INTER_NEAREST (resize.py:113-120).  The kernel sees no offset, flip or scale:
+ *   the caller evaluates OpenCV's index and weight rules on the host and supplies, per sample, the
+ *   tables of the crop window in OUTPUT coordinates (the column tables of a flipped sample
+ *   reversed).  A batch that needs no resize takes nmsa_batch_augment.
+ *   staging_host   PINNED host memory, n_words 32-bit words, 16-byte aligned: n_desc descriptors
+ *                  (24 words each), then six int32 tables for the n_samples samples and the h x w
+ *                  window that all descriptors share:
+ *                    col_near [n_samples, w]   nearest source column
+ *                    col_taps [n_samples, w]   i0 | i1 << 16: the two source columns of INTER_LINEAR
+ *                    col_wts  [n_samples, w]   a0 | a1 << 16: their weights, a0 + a1 == 2048
+ *                    row_near, row_taps, row_wts [n_samples, h]   the same for the rows
+ *   staging_device device memory of the same size, 16-byte aligned; the call enqueues ONE
+ *                  asynchronous copy of the staging buffer and the launch.  `block_begin` and
+ *                  `pixels_per_lane` of every descriptor are written by the call.
+ *   mode NMSA_AUGMENT_MOVE        dst[b, c, y, x] = src[b, row_near[b, y], col_near[b, x], c] as
+ *                                 raw bits of 1 << log2_size bytes, any channel count
+ *        NMSA_AUGMENT_DEPTH_NORM  the same gather, then as nmsa_batch_augment
+ *        NMSA_AUGMENT_RGB_NORM    uint8 only.  Per channel, with (i0, i1, a0, a1) of the column
+ *                                 and (j0, j1, b0, b1) of the row, in integer arithmetic as
+ *                                 OpenCV's 8-bit INTER_LINEAR:
+ *                                   R0 = S[j0, i0] * a0 + S[j0, i1] * a1, R1 the same in row j1,
+ *                                   v = (((b0 * (R0 >> 4)) >> 16) + ((b1 * (R1 >> 4)) >> 16) + 2) >> 2
+ *                                 then (float(v) - mean[c]) / std[c] as nmsa_batch_augment.
+ *   Every field and every table entry is checked on the host copy before anything is enqueued:
+ *   NMSA_ERR_ARG for what nmsa_batch_augment refuses in a descriptor, for descriptors that do not
+ *   share one h x w, for a nearest entry outside [0, H) / [0, W) of any descriptor, a tap outside
+ *   [0, H) / [0, W) of an RGB_NORM descriptor, an RGB_NORM source side above 65536, a weight above
+ *   2048, staging that is not 16-byte aligned, n_words below the descriptors and the tables.
+ *   NMSA_ERR_UNSUPPORTED for out_dtype NMSA_F16.  No workspace, no host synchronisation;
+ *   capturable in a hipGraph (tables written into the pinned buffer between replays are NOT
+ *   checked again: the writer runs these checks).
+ * ------------------------------------------------------------------------- */
+typedef struct nmsa_augment_resize_desc {
+    uint64_t src;               /* device address of the source, [B, H, W, C]                  */
+    uint64_t dst;               /* device address of the destination, [B, C, h, w]             */
+    int32_t B;                  /* samples: equals n_samples                                   */
+    int32_t H, W;               /* source side lengths (what the table entries index)          */
+    int32_t C;                  /* interleaved channels of the source, planes of the result    */
+    int32_t h, w;               /* crop window side lengths: the same in every descriptor      */
+    int32_t mode;               /* NMSA_AUGMENT_*                                              */
+    int32_t log2_size;          /* log2 of the SOURCE element size in bytes                    */
+    int32_t out_dtype;          /* NMSA_F32 (the normalising modes)                            */
+    int32_t raw_depth;          /* DEPTH_NORM: keep invalid_depth_value                        */
+    int32_t block_begin;        /* first workgroup of this descriptor: written by the call     */
+    int32_t pixels_per_lane;    /* 4 where w % 4 == 0 and dst allows vector stores, else 1:
+                                   written by the call                                         */
+    float mean[3];              /* RGB_NORM: per channel; DEPTH_NORM: [0]                      */
+    float std[3];
+    float invalid_depth_value;
+    int32_t reserved;
+} nmsa_augment_resize_desc;
+int nmsa_batch_augment_resized(void* staging_host, void* staging_device, int n_desc, int n_samples,
+                               int n_words, nmsa_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * scene classification (csrc/scene.hip)
  *
  * nmsa_scene_step: the scene task's whole step in ONE launch of one workgroup — softmax score and

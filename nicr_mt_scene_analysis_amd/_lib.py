@@ -136,6 +136,7 @@ _SIGNATURES = {
                                       _i, _vp, _vp, _vp, _vp]),
     'nmsa_multiscale_nearest': (_i, [_vp, _vp, _i, _i, _vp]),
     'nmsa_batch_augment': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'nmsa_batch_augment_resized': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'nmsa_scene_step': (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nmsa_upsample2x_dw3x3_route': (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
     'nmsa_upsample2x_dw3x3_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -33,7 +33,12 @@
 // No host synchronisation; capturable in a hipGraph (the copy node re-reads the pinned buffer at
 // replay: a captured call needs a staging buffer of its own, and whoever rewrites its parameter
 // words between replays owns the window checks).
-#include "nmsa_common.hpp"
+//
+// The sibling augment_resize.hip runs the same chain behind RandomResize, or behind the upscale of
+// an image smaller than the crop: it reads the source through per-sample index and weight tables
+// and shares this file's lane mapping and its element operations (augment_ops.hpp).  A batch that
+// needs no resize takes this file's kernel.
+#include "augment_ops.hpp"
 
 #include <string.h>
 
@@ -44,29 +49,6 @@ constexpr int AUG_THREADS = 256;
 constexpr int AUG_DESC_WORDS = 24;
 
 static_assert(sizeof(nmsa_augment_desc) == AUG_DESC_WORDS * 4, "the staging layout is 24 words per descriptor");
-
-struct op_move {
-    template <typename T>
-    __device__ __forceinline__ T operator()(T v, int) const { return v; }
-};
-
-// one IEEE subtract, then one IEEE divide (the file is built with -ffp-contract=off)
-struct op_rgb_norm {
-    float mean[3], std[3];
-    __device__ __forceinline__ float operator()(uint8_t v, int c) const { return ((float)v - mean[c]) / std[c]; }
-};
-
-struct op_depth_norm {
-    float mean, std, invalid;
-    bool raw;
-    template <typename T>
-    __device__ __forceinline__ float operator()(T v, int) const
-    {
-        const float f = (float)v;
-        // the test is on the source value: -0.0 == 0.0 comes out as the invalid value itself (+0.0)
-        return (raw && f == invalid) ? invalid : (f - mean) / std;
-    }
-};
 
 // S source element, D destination element, CT channels (0: read from the descriptor), NP pixels per lane
 template <typename S, typename D, int CT, int NP, typename Op>

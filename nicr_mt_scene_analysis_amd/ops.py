@@ -858,11 +858,11 @@ class AugmentStaging:
     def __init__(self, sig, B, source_hw, crop_hw, dev) -> None:
         (H, W), (h, w) = source_hw, crop_hw
         self.B, self.source_hw, self.crop_hw, self.n_desc = B, source_hw, crop_hw, len(sig)
-        self.host = torch.empty((self.n_desc * _AUG_DESC_WORDS + 3 * B,), dtype=torch.int32).pin_memory()
+        self.host = torch.empty((self.n_desc * _AUG_DESC_WORDS + self._tail_words(),), dtype=torch.int32).pin_memory()
         packed = self.host.numpy()
         packed[:] = 0
         table = packed[:self.n_desc * _AUG_DESC_WORDS].reshape(self.n_desc, _AUG_DESC_WORDS)
-        self.params = packed[self.n_desc * _AUG_DESC_WORDS:].reshape(B, 3)
+        self._bind_tail(packed[self.n_desc * _AUG_DESC_WORDS:])
         self.outputs, self.nbytes = [], 0
         for i, (name, shape, dtype, mode, consts) in enumerate(sig):
             C = shape[3] if len(shape) == 4 else 1
@@ -886,27 +886,21 @@ class AugmentStaging:
         self.device = torch.empty_like(self.host, device=dev)
         self.event = None
 
+    def _tail_words(self) -> int:
+        return 3 * self.B
+
+    def _bind_tail(self, tail: np.ndarray) -> None:
+        self.params = tail.reshape(self.B, 3)
+
     def write_params(self, params) -> None:
         """(y0, x0, flip) per sample for the next replay of the graph that captured this staging;
         checked here, because a replay does not pass through the entry point's checks again"""
         self.params[:] = check_augment_params(params, self.B, self.source_hw, self.crop_hw)
 
 
-def batch_augment(tensors: Dict[str, torch.Tensor], params, crop_hw: Tuple[int, int],
-                  norm: Optional[Dict[str, tuple]] = None, return_staging: bool = False):
-    """reference: RandomCrop (crop.py:57-73) -> RandomHorizontalFlip (flip.py:40-47) ->
-    NormalizeRGB / NormalizeDepth (normalize.py) -> ToTorchTensors (torch.py:31-38), for a whole
-    collated batch by ONE launch of nmsa_batch_augment behind one asynchronous copy of the
-    descriptor table.  `tensors`: contiguous [B,H,W] or channels-last [B,H,W,C] device tensors of
-    one B, H, W.  `params`: integer [B,3], (y0, x0, flip) per sample.  `norm[name]` is
-    ('rgb_norm', mean[3], std[3]) for a uint8 [B,H,W,3] entry or ('depth_norm', mean, std,
-    raw_depth, invalid_depth_value) for a uint16 / float32 [B,H,W] entry; the constants are used as
-    float32.  Every other entry moves as raw bits of 1, 2, 4 or 8 bytes.  -> {name: [B,h,w] for
-    [B,H,W], [B,C,h,w] for [B,H,W,C], float32 [B,3,h,w] / [B,1,h,w] for the normalised entries};
-    the outputs of one call are views of one allocation.  With `return_staging` the
-    `AugmentStaging` used comes back as well (under capture: the one the graph keeps reading)."""
-    h, w = int(crop_hw[0]), int(crop_hw[1])
-    norm = norm or {}
+def _augment_signature(tensors: Dict[str, torch.Tensor], norm: Dict[str, tuple]):
+    """the tensors of one augmentation call checked against each other and against `norm`
+    -> ([(name, shape, dtype, mode, constants)], device, (B, H, W))"""
     sig, dev, BHW = [], None, None
     for name, t in tensors.items():
         _require_on_device(t, name)
@@ -944,51 +938,258 @@ def batch_augment(tensors: Dict[str, torch.Tensor], params, crop_hw: Tuple[int, 
         sig.append((name, tuple(int(n) for n in t.shape), t.dtype, spec[0], consts))
     if set(norm) - set(tensors):
         raise KeyError(f'norm names entries that are not in tensors: {sorted(set(norm) - set(tensors))}')
-    if not sig:
-        return ({}, None) if return_staging else {}
     if len(sig) > 256:                                            # NMSA_AUGMENT_MAX_DESC
         raise ValueError('more than 256 keys in one call')
+    return sig, dev, BHW
+
+
+def _augment_launch(what: str, cache, captured: list, staging_type, tensors, sig, dev, BHW, crop_hw, write, entry):
+    """one launch of `entry` for `sig` from the staging of its shape set (LRU of 8 in `cache`, a
+    capture's in `captured`); `write(staging)` fills in the call's parameters -> (outputs, staging)"""
     B, H, W = BHW
-    if h <= 0 or w <= 0 or h > H or w > W:
-        raise ValueError(f'a crop of {h} x {w} does not fit the {H} x {W} source')
-    table = check_augment_params(params, B, (H, W), (h, w))
+    h, w = crop_hw
     capturing = torch.cuda.is_current_stream_capturing()
     shape_set = (dev, h, w, tuple(sig))
     if capturing:
         # (why: see multiscale_nearest)
-        key = next((k for k in _AUG_STAGING if k[:-1] == shape_set), None)
+        key = next((k for k in cache if k[:-1] == shape_set), None)
         if key is None:
-            raise RuntimeError('batch_augment under hipGraph capture: call it once with these shapes '
+            raise RuntimeError(f'{what} under hipGraph capture: call it once with these shapes '
                                'before the capture (its pinned staging cannot be allocated while a '
                                'stream captures)')
-        st = _AUG_STAGING.pop(key)
-        _AUG_CAPTURED.append(st)
+        st = cache.pop(key)
+        captured.append(st)
     else:
         key = shape_set + (torch.cuda.current_stream(dev).cuda_stream,)
-        st = _AUG_STAGING.get(key)
+        st = cache.get(key)
         if st is None:
-            st = _AUG_STAGING[key] = AugmentStaging(sig, B, (H, W), (h, w), dev)
-            while len(_AUG_STAGING) > 8:
-                _, dropped = _AUG_STAGING.popitem(last=False)
+            st = cache[key] = staging_type(sig, B, (H, W), (h, w), dev)
+            while len(cache) > 8:
+                _, dropped = cache.popitem(last=False)
                 if dropped.event is not None:
                     dropped.event.synchronize()         # its last copy still reads the pinned words
         else:
-            _AUG_STAGING.move_to_end(key)
+            cache.move_to_end(key)
             if st.event is not None:
                 st.event.synchronize()                  # the copy of the call before has run
     out = torch.empty((st.nbytes,), dtype=torch.uint8, device=dev)
     base = out.data_ptr()
     for i, (name, shape, dtype, at, nbytes) in enumerate(st.outputs):
         st.addresses[i] = (tensors[name].data_ptr(), base + at)
-    st.params[:] = table
-    L.check(L.lib().nmsa_batch_augment(
-        st.host_ptr, L.ptr(st.device), st.n_desc, B, int(st.host.numel()), L.stream_ptr(dev)),
-        'nmsa_batch_augment')
+    write(st)
+    L.check(entry(st.host_ptr, L.ptr(st.device), st.n_desc, B, int(st.host.numel()), L.stream_ptr(dev)), 'nmsa_' + what)
     if not capturing:
         if st.event is None:
             st.event = torch.cuda.Event()
         st.event.record(torch.cuda.current_stream(dev))
-    result = {name: out[at:at + nbytes].view(dtype).view(shape) for name, shape, dtype, at, nbytes in st.outputs}
+    return {name: out[at:at + nbytes].view(dtype).view(shape) for name, shape, dtype, at, nbytes in st.outputs}, st
+
+
+def batch_augment(tensors: Dict[str, torch.Tensor], params, crop_hw: Tuple[int, int],
+                  norm: Optional[Dict[str, tuple]] = None, return_staging: bool = False):
+    """reference: RandomCrop (crop.py:57-73) -> RandomHorizontalFlip (flip.py:40-47) ->
+    NormalizeRGB / NormalizeDepth (normalize.py) -> ToTorchTensors (torch.py:31-38), for a whole
+    collated batch by ONE launch of nmsa_batch_augment behind one asynchronous copy of the
+    descriptor table.  `tensors`: contiguous [B,H,W] or channels-last [B,H,W,C] device tensors of
+    one B, H, W.  `params`: integer [B,3], (y0, x0, flip) per sample.  `norm[name]` is
+    ('rgb_norm', mean[3], std[3]) for a uint8 [B,H,W,3] entry or ('depth_norm', mean, std,
+    raw_depth, invalid_depth_value) for a uint16 / float32 [B,H,W] entry; the constants are used as
+    float32.  Every other entry moves as raw bits of 1, 2, 4 or 8 bytes.  -> {name: [B,h,w] for
+    [B,H,W], [B,C,h,w] for [B,H,W,C], float32 [B,3,h,w] / [B,1,h,w] for the normalised entries};
+    the outputs of one call are views of one allocation.  With `return_staging` the
+    `AugmentStaging` used comes back as well (under capture: the one the graph keeps reading)."""
+    h, w = int(crop_hw[0]), int(crop_hw[1])
+    sig, dev, BHW = _augment_signature(tensors, norm or {})
+    if not sig:
+        return ({}, None) if return_staging else {}
+    B, H, W = BHW
+    if h <= 0 or w <= 0 or h > H or w > W:
+        raise ValueError(f'a crop of {h} x {w} does not fit the {H} x {W} source')
+    table = check_augment_params(params, B, (H, W), (h, w))
+
+    def write(st):
+        st.params[:] = table
+    result, st = _augment_launch('batch_augment', _AUG_STAGING, _AUG_CAPTURED, AugmentStaging, tensors, sig, dev,
+                                 BHW, (h, w), write, L.lib().nmsa_batch_augment)
+    return (result, st) if return_staging else result
+
+
+# ----------------------------------------------------------------------------- batch augmentation behind a resize
+# OpenCV's resize rules for ONE side of an image, evaluated for a window of destination indices of
+# several samples at once.  cv2_nearest_map above, cv2_nearest_map_vec and cv2_linear_taps below are
+# the ONLY places these rules live in the package; the device reads tables.  Both rules are written
+# down from OpenCV's source and have NOT been compared with a real cv2 build (none is installed
+# where this project is developed); a later comparison touches these functions and the stand-in of
+# tools/gen_golden_augment_resize.py, and nothing else.
+_CV2_COEF_ONE = 2048        # INTER_RESIZE_COEF_SCALE: the 8-bit linear path's weights are 11-bit fixed point
+
+
+def _window_positions(start, n: int) -> np.ndarray:
+    """f64 [B, n]: the destination indices start[b] .. start[b] + n"""
+    return np.asarray(start, np.float64)[:, None] + np.arange(n, dtype=np.float64)
+
+
+def _cv2_nearest_window(src: int, dst, at: np.ndarray) -> np.ndarray:
+    """i32 [B, n]: entries at[b] (`_window_positions`, left as they are) of cv2_nearest_map(src, dst[b])"""
+    ifx = 1.0 / (np.asarray(dst, np.float64)[:, None] / float(src))
+    x = at * ifx
+    return np.minimum(np.floor(x, out=x), src - 1, out=x).astype(np.int32)
+
+
+def _cv2_linear_window(src: int, dst, at: np.ndarray):
+    """(i0, i1 i32 [B, n], a0, a1 i16 [B, n]): entries at[b] of cv2_linear_taps(src, dst[b])"""
+    scale = 1.0 / (np.asarray(dst, np.float64)[:, None] / float(src))
+    d = at + 0.5
+    d *= scale
+    d -= 0.5
+    f = d.astype(np.float32)
+    floor = np.floor(f)
+    f -= floor                                                    # float32, as OpenCV's `fx -= sx`
+    s = floor.astype(np.int32)
+    f[(s < 0) | (s >= src - 1)] = 0
+    np.clip(s, 0, src - 1, out=s)
+    a1 = np.rint(f * np.float32(_CV2_COEF_ONE)).astype(np.int16)
+    np.subtract(np.float32(1.0), f, out=f)
+    f *= np.float32(_CV2_COEF_ONE)
+    return s, np.minimum(s + 1, src - 1), np.rint(f, out=f).astype(np.int16), a1
+
+
+def _check_sides(src: int, dst: int) -> Tuple[int, int]:
+    src, dst = int(src), int(dst)
+    if src < 1 or dst < 1:
+        raise ValueError(f'side lengths must be positive, got {src} -> {dst}')
+    return src, dst
+
+
+def cv2_nearest_map_vec(src: int, dst: int) -> np.ndarray:
+    """`cv2_nearest_map(src, dst)` without the Python loop (the same double arithmetic in numpy)"""
+    src, dst = _check_sides(src, dst)
+    return _cv2_nearest_window(src, [dst], _window_positions([0], dst))[0]
+
+
+def cv2_linear_taps(src: int, dst: int):
+    """Taps of a bilinear resize (cv2.INTER_LINEAR) of one side of a uint8 image from `src` to
+    `dst` elements, as OpenCV's generic 8-bit path computes them -> (i0, i1, a0, a1): per
+    destination index d the two source indices (int32) and their weights of 2048 (int16).
+      scale = 1 / (dst / src) in double; f = float32((d + 0.5) * scale - 0.5); s = floor(f);
+      f -= s in float32; s < 0: f = 0, s = 0; s >= src - 1: f = 0, s = src - 1;
+      i0 = s, i1 = min(s + 1, src - 1), a0 = rint((1 - f) * 2048), a1 = rint(f * 2048)
+    A pixel is R = S[i0] * a0 + S[i1] * a1 along a row, then with the row taps (b0, b1)
+    (((b0 * (R0 >> 4)) >> 16) + ((b1 * (R1 >> 4)) >> 16) + 2) >> 2.  At dst == src this is the
+    image itself and at an exact 2:1 downscale (a + b + c + d + 2) >> 2, which is what OpenCV's
+    area path computes where it takes over INTER_LINEAR.  Written down from OpenCV's source, NOT
+    compared with a real cv2 build."""
+    src, dst = _check_sides(src, dst)
+    return tuple(a[0] for a in _cv2_linear_window(src, [dst], _window_positions([0], dst)))
+
+
+def check_augment_resize_params(params, B: int, crop_hw: Tuple[int, int]) -> np.ndarray:
+    """`params` as the int32 [B,5] table of (y0, x0, flip, rh, rw) per sample: resized sizes of at
+    least 1, every crop window inside its sample's resized image, every flip 0 or 1"""
+    table = np.asarray(params)
+    if table.shape != (B, 5) or table.dtype.kind not in 'iub':
+        raise ValueError(f'params must be {B} integer rows (y0, x0, flip, rh, rw), got {table.dtype} {table.shape}')
+    table = table.astype(np.int64)
+    h, w = crop_hw
+    if (table[:, 3:] < 1).any() or (table[:, 3:] > 0x7fffffff).any():
+        raise ValueError(f'resized sizes must be at least 1 (and below 2^31): {table[:, 3:].tolist()}')
+    if (table[:, :2] < 0).any() or (table[:, 0] + h > table[:, 3]).any() or (table[:, 1] + w > table[:, 4]).any():
+        raise ValueError(f'a crop window of {h} x {w} leaves its resized image: {table.tolist()}')
+    if not np.isin(table[:, 2], (0, 1)).all():
+        raise ValueError(f'flip must be 0 or 1, got {table[:, 2].tolist()}')
+    return table.astype(np.int32)
+
+
+def augment_window_tables(params, source_hw: Tuple[int, int], crop_hw: Tuple[int, int], check: bool = True):
+    """The tables nmsa_batch_augment_resized reads, for the [B,5] table (y0, x0, flip, rh, rw):
+    per sample the crop window [y0, y0 + h) x [x0, x0 + w) of the image resized from `source_hw`
+    to (rh, rw), in OUTPUT coordinates — the column tables of a flipped sample are reversed, so
+    the kernel sees no offset and no flip.  -> (cols i32 [3, B, w], rows i32 [3, B, h]), each
+    (nearest index, i0 | i1 << 16, a0 | a1 << 16).  On a source side above 65536 the taps do not
+    fit their half words and are left 0 (`batch_augment_resized` then refuses rgb).  With `check`
+    the entry point's table checks are run here, with a message: for whoever writes the tables
+    where no entry point follows (`AugmentResizeStaging.write_params`)."""
+    H, W = int(source_hw[0]), int(source_hw[1])
+    h, w = int(crop_hw[0]), int(crop_hw[1])
+    if H < 1 or W < 1 or h < 1 or w < 1:
+        raise ValueError(f'side lengths must be positive, got {H} x {W} and {h} x {w}')
+    table = check_augment_resize_params(params, len(np.asarray(params)), (h, w))
+    y0, x0, flip, rh, rw = table.T
+    out = []
+    for src, dst, start, n in ((W, rw, x0, w), (H, rh, y0, h)):
+        tables = np.zeros((3, len(table), n), np.int32)
+        at = _window_positions(start, n)
+        tables[0] = _cv2_nearest_window(src, dst, at)
+        if src <= 65536:
+            i0, i1, a0, a1 = _cv2_linear_window(src, dst, at)
+            # (half words of a little-endian word: low, high)
+            packed = tables[1:].view(np.uint16).reshape(2, len(table), n, 2)
+            packed[0, ..., 0], packed[0, ..., 1], packed[1, ..., 0], packed[1, ..., 1] = i0, i1, a0, a1
+            if check and (min(i0.min(), i1.min()) < 0 or max(i0.max(), i1.max()) >= src or
+                          min(a0.min(), a1.min()) < 0 or max(a0.max(), a1.max()) > _CV2_COEF_ONE):
+                raise ValueError(f'a linear tap leaves the source side of {src}')
+        if check and (tables[0].min() < 0 or tables[0].max() >= src):
+            raise ValueError(f'a nearest index leaves the source side of {src}')
+        out.append(tables)
+    cols, rows = out
+    flipped = flip != 0
+    cols[:, flipped] = cols[:, flipped, ::-1]
+    return cols, rows
+
+
+_AUGR_STAGING: 'collections.OrderedDict[tuple, AugmentResizeStaging]' = __import__('collections').OrderedDict()
+_AUGR_CAPTURED = []
+
+
+class AugmentResizeStaging(AugmentStaging):
+    """Staging of one shape set of `batch_augment_resized`: as `AugmentStaging`, with the window
+    tables of `augment_window_tables` behind the descriptors in place of the parameter triples
+    (nmsa_augment_resize_desc has the layout of nmsa_augment_desc)."""
+
+    def _tail_words(self) -> int:
+        return 3 * self.B * (self.crop_hw[0] + self.crop_hw[1])
+
+    def _bind_tail(self, tail: np.ndarray) -> None:
+        h, w = self.crop_hw
+        self.cols = tail[:3 * self.B * w].reshape(3, self.B, w)
+        self.rows = tail[3 * self.B * w:].reshape(3, self.B, h)
+
+    def write_params(self, params) -> None:
+        """(y0, x0, flip, rh, rw) per sample for the next replay of the graph that captured this
+        staging: the tables are built and checked first (a replay does not pass through the entry
+        point's checks), and written only when they pass"""
+        if len(np.asarray(params)) != self.B:
+            raise ValueError(f'params must have {self.B} rows')
+        self.cols[:], self.rows[:] = augment_window_tables(params, self.source_hw, self.crop_hw)
+
+
+def batch_augment_resized(tensors: Dict[str, torch.Tensor], params, crop_hw: Tuple[int, int],
+                          norm: Optional[Dict[str, tuple]] = None, return_staging: bool = False):
+    """reference: RandomResize (resize.py:311-340) or RandomCrop's upscale (crop.py:43-55), then
+    the chain of `batch_augment`, for a whole collated batch by ONE launch of
+    nmsa_batch_augment_resized behind one asynchronous copy of the descriptors and the window
+    tables; the resized images are never formed.  `params`: integer [B,5], (y0, x0, flip, rh, rw)
+    per sample — the source resized to rh x rw (cv2.INTER_LINEAR for the 'rgb_norm' entry,
+    cv2.INTER_NEAREST for every other, resize.py:113-120), cropped to `crop_hw` at (y0, x0), then
+    flipped.  `tensors`, `norm`, the result and `return_staging` (an `AugmentResizeStaging`) as
+    `batch_augment`.  This wrapper always takes the resize kernel, also where rh x rw is the
+    source's size (the result is then `batch_augment`'s, bit for bit)."""
+    h, w = int(crop_hw[0]), int(crop_hw[1])
+    sig, dev, BHW = _augment_signature(tensors, norm or {})
+    if not sig:
+        return ({}, None) if return_staging else {}
+    B, H, W = BHW
+    if max(H, W) > 65536 and any(mode == 'rgb_norm' for _, _, _, mode, _ in sig):
+        raise ValueError(f'rgb_norm behind a resize takes sources of at most 65536 a side, got {H} x {W}')
+    if len(np.asarray(params)) != B:
+        raise ValueError(f'params must have {B} rows')
+    # (the entry point checks every table entry)
+    cols, rows = augment_window_tables(params, (H, W), (h, w), check=False)
+
+    def write(st):
+        st.cols[:], st.rows[:] = cols, rows
+    result, st = _augment_launch('batch_augment_resized', _AUGR_STAGING, _AUGR_CAPTURED, AugmentResizeStaging, tensors,
+                                 sig, dev, BHW, (h, w), write, L.lib().nmsa_batch_augment_resized)
     return (result, st) if return_staging else result
 
 

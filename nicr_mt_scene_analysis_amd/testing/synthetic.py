@@ -663,6 +663,10 @@ def make_augment_inputs(recipe: str, seed: int) -> Dict:
     `make_multiscale_inputs`, `segment_ids` u32 [B,H,W] above 2^16 (the device batch holds it as
     i64) and `orientations`, one dict {instance id: angle} per image."""
     B, C, H, W, n_inst, _, _, _, depth_dtype, depth_mean = AUGMENT_RECIPES[AUGMENT_RECIPES[recipe][12]][:10]
+    return _make_raw_batch(B, C, H, W, n_inst, depth_dtype, depth_mean, seed)
+
+
+def _make_raw_batch(B: int, C: int, H: int, W: int, n_inst: int, depth_dtype: str, depth_mean: float, seed: int) -> Dict:
     maps = make_label_maps(B, C, H, W, n_instances=n_inst, seed=seed, max_radius=max(4, min(H, W) // 3))
     sem, ins = maps['semantic'], maps['instance']
     rng = np.random.default_rng(seed + 15485863)
@@ -699,6 +703,34 @@ def augment_input_digest(inp: Dict) -> str:
     angles = json.dumps([[[int(k), float(v)] for k, v in d.items()] for d in inp['orientations']])
     return input_digest(*(inp[k] for k in AUGMENT_SPATIAL_KEYS), inp['semantic_classes_is_thing'],
                         np.frombuffer(angles.encode(), dtype=np.uint8))
+
+
+# ---- batch augmentation behind a resize (data/preprocessing/{resize,crop,flip,normalize,torch}.py) ----
+# recipe -> B, n_classes, H, W, random instances per image, crop, flip p, depth (dtype, mean, std,
+# raw_depth), then ONE of: scales (min, max) of RandomResize; sizes [(rh, rw)] per sample, applied
+# with the reference's resize() in RandomResize's place; upscale (RandomCrop resizes the image that
+# is smaller than the crop).  The keys are AUGMENT_SPATIAL_KEYS.
+_U16_DEPTH = ('uint16', 2841.94941272766, 1417.2594281672277, False)
+AUGMENT_RESIZE_RECIPES = {
+    # w % 4 == 0: four pixels per lane; both flip values, both parities of x0, scales below and above 1
+    'RA': dict(B=4, C=9, H=41, W=67, n_inst=10, crop=(21, 36), p=0.5, depth=_U16_DEPTH, scales=(0.6, 1.5)),
+    # w % 4 == 2: one pixel per lane
+    'RB': dict(B=3, C=9, H=41, W=67, n_inst=10, crop=(19, 38), p=0.5, depth=_U16_DEPTH, scales=(0.6, 1.5)),
+    # an exact 2:1 downscale, no scale draw, no offset draws: rgb is the mean of 2 x 2 pixels
+    'RC': dict(B=2, C=9, H=40, W=64, n_inst=8, crop=(20, 32), p=0.5, depth=_U16_DEPTH, scales=(0.5, 0.5)),
+    # nearest maps that differ from x * src // dst on both sides (36 -> 44, 63 -> 77; 36 -> 28, 63 -> 49)
+    'RD': dict(B=2, C=9, H=36, W=63, n_inst=8, crop=(24, 44), p=0.5, depth=_U16_DEPTH, sizes=((44, 77), (28, 49))),
+    # smaller than the crop: upscaled to 35 x 40, x0 is not drawn; float32 depth with invalid values kept
+    'RE': dict(B=2, C=9, H=20, W=23, n_inst=6, crop=(33, 40), p=0.5, depth=('float32', 1.5, 0.75, True), upscale=True),
+    # rows longer than a wave of four-pixel lanes, several blocks per descriptor
+    'RF': dict(B=2, C=9, H=12, W=301, n_inst=8, crop=(10, 300), p=0.5, depth=_U16_DEPTH, scales=(1.0, 1.4)),
+}
+
+
+def make_augment_resize_inputs(recipe: str, seed: int) -> Dict:
+    """the raw batch of `make_augment_inputs` for a recipe of AUGMENT_RESIZE_RECIPES"""
+    r = AUGMENT_RESIZE_RECIPES[recipe]
+    return _make_raw_batch(r['B'], r['C'], r['H'], r['W'], r['n_inst'], r['depth'][0], r['depth'][1], seed)
 
 
 # ----------------------------------------------------------------------------- scene task
